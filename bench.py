@@ -2,13 +2,16 @@
 """Headline benchmark: captcha images/sec in TRAINING (forward + CTC + backward + all-reduce + clip + Adam) of the
 VGG-7 + BiLSTM(256) + CTC CRNN at H=32, W=256, 10-char labels, batch 64 per GPU (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
-One JSON line on rank 0.  `roofline` is the dominant kernel (conv_k3 / conv_k2 / conv_halo: implicit-GEMM 3x3 convolution, MFMA-bound), timed
-live with HIP events on the launch stream; `cpu_baseline` is the CPU oracle (a torch-CPU restatement of the
-reference TF1 graph — the TF reference itself cannot run here) on a bounded sample of the same workload.
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`);
+--dump-outputs DIR also writes what the last timed step computed (parameters, gradients, loss) as DIR/<name>.npy.
+--full adds the side measurements: the same loop with the loss fetched every step and one step behind, `roofline` (the dominant
+kernel: conv_k3 / conv_k2 / conv_halo, implicit-GEMM 3x3 convolution, MFMA-bound, timed live with HIP events on the launch stream,
+plus the weight gradients) and `cpu_baseline` (the CPU oracle: a torch-CPU restatement of the reference TF1 graph — the TF reference
+itself cannot run here — on a bounded sample of the same workload).
 """
 import argparse
 import glob
@@ -387,6 +390,29 @@ def cpu_baseline(budget_s=12.0):
             "c1_sample": "BASELINE configs[0]: %d training steps / %d forward+greedy-decode passes of 8 images (W=88, L=4)" % (c1_steps, reps)}
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(eng, out_dir, loss):
+    """What the last timed step left for its caller, as DIR/<name>.npy: the flat parameter vector after the update (float32), the
+    gradient it applied (float32) and loss = [total, ctc, l2 term, gradient norm] (float64).  An array whose share of the 64 MB budget
+    is smaller than itself is written as a fixed sample (seed 0, sorted indices), its indices beside it as <name>_index.npy.
+    The inputs and the initial parameters are the same in every run with the same arguments, and the headline (fixed) workload's step adds
+    its split partial sums in a fixed order (no order-dependent float atomics), so two runs of it write the same bits."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss, eng.last_ctc, eng.last_reg, eng.last_gnorm], dtype=np.float64))
+    flat = {"params": eng.params, "grads": eng.grads}
+    share = (DUMP_BUDGET_BYTES - 4096) // len(flat)
+    for name, t in flat.items():
+        t = t.detach().reshape(-1).float()
+        if t.numel() * 4 > share:
+            # (the index array is int64: value + index = 12 bytes per sampled element)
+            idx = np.sort(np.random.RandomState(0).choice(t.numel(), share // 12, replace=False))
+            np.save(os.path.join(out_dir, "%s_index.npy" % name), idx.astype(np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, "%s.npy" % name), t.cpu().numpy().astype(np.float32))
+
+
 def self_launch(n):
     """Re-run this command line as n ranks under `python -m torch.distributed.run` on a free local port and pass the exit code on.
     Refuses when the box shows fewer GPUs than ranks (except with OCR_DIST_BACKEND=gloo, the test transport that shares one GPU)."""
@@ -407,9 +433,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=None, help="ranks = GPUs of this node (default: WORLD_SIZE under a launcher, else 1)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements: the loop with the loss fetched every step and one step "
+                         "behind, the convolution roofline and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (parameters, gradients, loss) to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graphs", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the live per-launch timing of the dominant kernel (profiling runs)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the live per-launch timing of the dominant kernel (profiling runs)")
     ap.add_argument("--batch", type=int, default=None,
                     help="images per GPU and step (default: the workload's own — 64, deep 32).  Any other value is a SIDE measurement: the line "
                          "says so in `metric` and `config` and is never the headline number")
@@ -520,30 +551,34 @@ def main():
         ls = torch.tensor([loss], dtype=torch.float64, device=device)
         llo, lhi = reduce_(ls.clone(), dist.ReduceOp.MIN), reduce_(ls.clone(), dist.ReduceOp.MAX)
         dp_check = {"replicas_bit_identical": bool(torch.equal(lo, hi)), "local_loss_min": float(llo.item()), "local_loss_max": float(lhi.item())}
-    # the same loop the way lib/lstm/train.py:130,139 runs it — the loss is fetched (one host sync) after EVERY step; reported
-    # beside `value`, never as `value`
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        x, labels, ll, sl = batches[i % len(batches)]
-        eng.train_step(x, labels, ll, sl, fetch_loss=True)
-    torch.cuda.synchronize()
-    dt_fetch = time.perf_counter() - t1
-    # ... and the way lstm_ctc_ocr_amd/train.py runs it by default: every loss is read, one iteration behind (OCR_LOSS_LAG=1)
-    t2 = time.perf_counter()
-    pending = None
-    for i in range(args.steps):
-        x, labels, ll, sl = batches[i % len(batches)]
-        eng.train_step(x, labels, ll, sl, fetch_loss=False)
-        h = eng.report_async()
-        if pending is not None:
-            eng.report_wait(pending)
-        pending = h
-    eng.report_wait(pending)
-    torch.cuda.synchronize()
-    dt_lag = time.perf_counter() - t2
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs, loss)      # before the side loops of --full train further
+    dt_fetch = dt_lag = None
+    if args.full:
+        # the same loop the way lib/lstm/train.py:130,139 runs it — the loss is fetched (one host sync) after EVERY step; reported
+        # beside `value`, never as `value`
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            x, labels, ll, sl = batches[i % len(batches)]
+            eng.train_step(x, labels, ll, sl, fetch_loss=True)
+        torch.cuda.synchronize()
+        dt_fetch = time.perf_counter() - t1
+        # ... and the way lstm_ctc_ocr_amd/train.py runs it by default: every loss is read, one iteration behind (OCR_LOSS_LAG=1)
+        t2 = time.perf_counter()
+        pending = None
+        for i in range(args.steps):
+            x, labels, ll, sl = batches[i % len(batches)]
+            eng.train_step(x, labels, ll, sl, fetch_loss=False)
+            h = eng.report_async()
+            if pending is not None:
+                eng.report_wait(pending)
+            pending = h
+        eng.report_wait(pending)
+        torch.cuda.synchronize()
+        dt_lag = time.perf_counter() - t2
 
-    g3 = eng.guard_counters()
+    g3 = eng.guard_counters() if args.full else g2
     guard = torch.tensor([g1[0] - g0[0], g2[0] - g1[0], g3[0] - g2[0], g1[1] - g0[1], g2[1] - g1[1], g3[1] - g2[1]], dtype=torch.float64, device=device)
     if world > 1:                       # (every rank drops the same steps; the time-out counts are per rank: the line carries the maximum)
         guard = reduce_(guard, dist.ReduceOp.MAX)
@@ -563,8 +598,8 @@ def main():
                                     "bs=32/GPU (BASELINE.json configs[4]; bf16 MFMA operands where BASELINE says fp16: same MFMA rate, fp32 accumulation)"),
                        "global_batch": BATCH * world, "parallelism": "dp%d" % world, "hipgraph": not args.no_graphs},
             "final_loss": loss,
-            "dropped_steps": {"warmup": guard[0], "timed": guard[1], "side_loops": guard[2]},
-            "lstm_timeouts": {"warmup": guard[3], "timed": guard[4], "side_loops": guard[5]},
+            "dropped_steps": dict({"warmup": guard[0], "timed": guard[1]}, **({"side_loops": guard[2]} if args.full else {})),
+            "lstm_timeouts": dict({"warmup": guard[3], "timed": guard[4]}, **({"side_loops": guard[5]} if args.full else {})),
             "guard": ("device-guarded optimiser step (ocr_optim_step_guarded2): on" if eng._guard_on() else "off (OCR_LSTM_TIMEOUT_GUARD=0): a time-out raises at the next report"),
             "fake_comm": ({"cus": int(os.environ["OCR_FAKE_COMM_CUS"]), "us_per_25mb": float(os.environ.get("OCR_FAKE_COMM_US", "250")),
                            "lds_kb": int(os.environ.get("OCR_FAKE_COMM_LDS_KB", "96")), "fake_world": int(os.environ["OCR_FAKE_WORLD"]),
@@ -576,10 +611,11 @@ def main():
                             else "three hipGraphs per step, the two bucket all-reduces issued between them" if eng.overlap_allreduce
                             else "two hipGraphs per step, one all-reduce between them (OCR_OVERLAP_ALLREDUCE=0)"),
             "dp_check": dp_check, "dp_host_enqueue_us": dp_host,
-            "with_loss_fetch_every_step": {"value": BATCH * world * args.steps / dt_fetch, "ms_per_step": dt_fetch / args.steps * 1e3},
-            "with_loss_read_one_step_behind": {"value": BATCH * world * args.steps / dt_lag, "ms_per_step": dt_lag / args.steps * 1e3},
             "model_tflops_per_gpu": value / world * TRAIN_GFLOP_PER_IMG * 1e9 / 1e12,
         }
+        if args.full:
+            line["with_loss_fetch_every_step"] = {"value": BATCH * world * args.steps / dt_fetch, "ms_per_step": dt_fetch / args.steps * 1e3}
+            line["with_loss_read_one_step_behind"] = {"value": BATCH * world * args.steps / dt_lag, "ms_per_step": dt_lag / args.steps * 1e3}
         if guard[1] or guard[4]:
             # work was skipped inside the timed region: no number
             line["value"] = None
@@ -600,7 +636,7 @@ def main():
             line["config"]["workload"] += " — run at bs=%d/GPU instead of %d" % (BATCH, default_batch)
         # the timed number above is complete at this point: a failure in the two side measurements must not cost the line (it is
         # reported inside the line instead of being swallowed)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 line["roofline"] = conv_roofline(eng, device, args.workload)
                 try:
@@ -621,7 +657,7 @@ def main():
                                              "pmc_error": "counter summaries are taken at the workload's own batch size (%d), this run is bs=%d" % (default_batch, BATCH)})
             except Exception as e:              # noqa: BLE001
                 line["roofline"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline()
             except Exception as e:          # noqa: BLE001

@@ -110,6 +110,12 @@ int ocr_conv3x3_relu_pool_bf16(const void* x, const void* wpack, void* y, void* 
  * colsum (may be NULL): colsum[j] += scale * sum_m B[m][j] — the bias gradient, produced by the same pass */
 int ocr_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb, float* out, long ldo, int Mk, int I, int J,
                      int row_group, int row_skip, long a_row_off, float scale, int splits, float* colsum, void* stream);
+/* The same product (plain rows: no row group, no offset) without float atomics: every split of the contraction stores its partial block
+ * to `part` and a second launch adds the splits in a fixed order, so out / colsum get the same bits in every run.  part holds at least
+ * ocr_gemm_tn_split_workspace_floats(Mk, I, J) floats (-1: invalid shape). */
+long ocr_gemm_tn_split_workspace_floats(int Mk, int I, int J);
+int ocr_gemm_tn_split_bf16(const void* A, long lda, const void* B, long ldb, float* out, long ldo, int Mk, int I, int J, float scale,
+                           float* colsum, float* part, long part_floats, void* stream);
 /* nbatch products of one shape in one launch; problem b: A + b*strideA, B + b*strideB, out + b*strideOut, colsum + b*strideColsum */
 int ocr_gemm_tn_batched_bf16(const void* A, long lda, long strideA, const void* B, long ldb, long strideB, float* out, long ldo,
                              long strideOut, int Mk, int I, int J, int nbatch, float scale, int splits, float* colsum,

@@ -33,6 +33,8 @@ struct TnArgs {
     long ldo;
     float scale;      // multiply before accumulation (e.g. 1.0)
     float* colsum;    // optional: colsum[j] += sum_m B[m][j]  (bias gradient fused into the weight-gradient pass)
+    float* part;      // plain mode, optional: split z of the contraction STORES its [I][J] block and [J] column sums to part + z * (I*J + J)
+                      // instead of adding them to out / colsum with atomics; tn_split_reduce_kernel then adds the splits in a fixed order
 };
 
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
@@ -171,9 +173,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs g) {
         if (tid < BJ && j0 + tid < g.J) {
             float t = 0.f;
             for (int u = tid >> 3; u < 256; u += CPB) t += red[u * 8 + (tid & 7)];
-            atomicAdd(g.colsum + j0 + tid, t * g.scale);
+            if (g.part) g.part[(long)blockIdx.z * ((long)g.I * g.J + g.J) + (long)g.I * g.J + j0 + tid] = t * g.scale;
+            else atomicAdd(g.colsum + j0 + tid, t * g.scale);
         }
     }
+    float* pz = g.part ? g.part + (long)blockIdx.z * ((long)g.I * g.J + g.J) : nullptr;
     // lane owns i = ib + (lane>>4)*4 + r, j = jb + (lane&15)
     float* out = g.out;
     long ldo = g.ldo;
@@ -187,7 +191,10 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs g) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 int i = i0 + wi * 16 * FI + a * 16 + (lane >> 4) * 4 + r;
-                if (i < g.I) atomicAdd(out + (long)i * ldo + j, acc[a][b][r] * g.scale);
+                if (i < g.I) {
+                    if (pz) pz[(long)i * g.J + j] = acc[a][b][r] * g.scale;
+                    else atomicAdd(out + (long)i * ldo + j, acc[a][b][r] * g.scale);
+                }
             }
         }
     }
@@ -240,6 +247,59 @@ extern "C" int ocr_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb
     if (splits <= 0) splits = pick_splits(tiles, Mk);
     g.k_per_split = ceil_div(ceil_div(Mk, splits), 32) * 32;
     return big ? launch_tn<0, 4, 4>(g, 1, (hipStream_t)stream) : launch_tn<0, 2, 2>(g, 1, (hipStream_t)stream);
+}
+
+// Deterministic form of the plain product: the contraction is split as ocr_gemm_tn_bf16 splits it, but every split stores its partial
+// block to the workspace and one more launch adds the splits in split order — no float atomics, so the result is the same in every run.
+__global__ __launch_bounds__(256) void tn_split_reduce_kernel(const float* __restrict__ part, int S, int I, int J, float* __restrict__ out,
+                                                              long ldo, float* __restrict__ colsum) {
+    const long IJ = (long)I * J, stride = IJ + J;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= stride || (e >= IJ && colsum == nullptr)) return;
+    // eight independent loads in flight per thread, added in split order (the order is what makes the result reproducible)
+    float t = 0.f;
+    int s = 0;
+    for (; s + 8 <= S; s += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = part[(long)(s + u) * stride + e];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t += v[u];
+    }
+    for (; s < S; ++s) t += part[(long)s * stride + e];
+    if (e < IJ) out[(e / J) * ldo + e % J] += t;
+    else colsum[e - IJ] += t;
+}
+
+static void tn_split_plan(int Mk, int I, int J, bool* big, int* k_per_split, int* S) {
+    *big = (I >= 128 && J >= 128);
+    long tiles = *big ? (long)ceil_div(I, 128) * ceil_div(J, 128) : (long)ceil_div(I, 64) * ceil_div(J, 64);
+    *k_per_split = ceil_div(ceil_div(Mk, pick_splits(tiles, Mk)), 32) * 32;
+    *S = ceil_div(Mk, *k_per_split);
+}
+
+extern "C" long ocr_gemm_tn_split_workspace_floats(int Mk, int I, int J) {
+    if (Mk <= 0 || I <= 0 || J <= 0) return -1;
+    bool big; int kps, S;
+    tn_split_plan(Mk, I, J, &big, &kps, &S);
+    return (long)S * ((long)I * J + J);
+}
+
+extern "C" int ocr_gemm_tn_split_bf16(const void* A, long lda, const void* B, long ldb, float* out, long ldo, int Mk, int I, int J,
+                                      float scale, float* colsum, float* part, long part_floats, void* stream) {
+    if (!A || !B || !out || !part || Mk <= 0 || I <= 0 || J <= 0 || (I & 7) || (J & 7) || ldo < J) return OCR_ERR_INVALID;
+    if (part_floats < ocr_gemm_tn_split_workspace_floats(Mk, I, J)) return OCR_ERR_INVALID;
+    TnArgs g = {};
+    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.lda = lda; g.ldb = ldb; g.Mk = Mk; g.I = I; g.J = J;
+    g.out = out; g.ldo = ldo; g.scale = scale; g.colsum = colsum; g.part = part;
+    bool big; int S;
+    tn_split_plan(Mk, I, J, &big, &g.k_per_split, &S);
+    int rc = big ? launch_tn<0, 4, 4>(g, 1, (hipStream_t)stream) : launch_tn<0, 2, 2>(g, 1, (hipStream_t)stream);
+    if (rc != OCR_OK) return rc;
+    const long n = (long)I * J + J;
+    tn_split_reduce_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, (hipStream_t)stream>>>(part, S, I, J, out, ldo, colsum);
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
 }
 
 // `nbatch` independent products of one shape in ONE launch: problem b uses A + b*strideA, B + b*strideB, out + b*strideOut,

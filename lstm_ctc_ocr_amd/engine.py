@@ -834,6 +834,8 @@ class _BiLstmOp(_Op):
         if self.with_fc:
             b[self.key + '/y'] = torch.empty((T, N, C), dtype=F32, device=dev)      # logits, time-major
             b[self.key + '/dy'] = torch.empty((R, C), dtype=BF16, device=dev)       # d loss / d logits, [N,T,C]
+            # split partials of the FC weight gradient (ops.gemm_tn_split: added in a fixed order, no float atomics)
+            b[self.key + '/fc_ws'] = torch.empty(ops.gemm_tn_split_workspace(R, ND * U, C), dtype=F32, device=dev)
         b[self.key + '/dhout'] = torch.empty((R, ND * U), dtype=BF16, device=dev)
         b[self.key + '/dz'] = torch.zeros((R, ND * 4 * U), dtype=BF16, device=dev)
         b[self.key + '/dc'] = torch.zeros((ND, N, U), dtype=F32, device=dev)
@@ -899,8 +901,8 @@ class _BiLstmOp(_Op):
         batched = (D + U) % 128 == 0 and (4 * U) % 128 == 0
         if self.with_fc:
             dl = b[self.key + '/dy']
-            # FC: dW += H^T dL, db += colsum dL, dH = dL Wfc^T
-            ops.gemm_tn(hout, dl, e.grad(self.fc + '/weights'), colsum=e.grad(self.fc + '/biases'))
+            # FC: dW += H^T dL, db += colsum dL, dH = dL Wfc^T  (the split contraction is added in a fixed order: the same bits every run)
+            ops.gemm_tn_split(hout, dl, e.grad(self.fc + '/weights'), b[self.key + '/fc_ws'], colsum=e.grad(self.fc + '/biases'))
             ops.gemm_nt(dl, e.shadow(self.fc + '/weights'), out=b[self.key + '/dhout'])
         # BPTT, all directions per launch
         wsh = e.shadow(self.cells[0] + '/weights')

@@ -164,6 +164,23 @@ def gemm_tn(A, B, out, *, Mk=None, I=None, J=None, lda=None, ldb=None, ldo=None,
     return out
 
 
+def gemm_tn_split_workspace(Mk, I, J):
+    """float32 elements of the workspace gemm_tn_split needs for this shape."""
+    n = nat.lib().ocr_gemm_tn_split_workspace_floats(int(Mk), int(I), int(J))
+    if n < 0:
+        raise nat.NativeError("ocr_gemm_tn_split_workspace_floats: invalid shape (%d, %d, %d)" % (Mk, I, J))
+    return int(n)
+
+
+def gemm_tn_split(A, B, out, ws, *, colsum=None, scale=1.0):
+    """out[I][J] (f32) += scale * A^T B and colsum[J] += scale * column sums of B, like gemm_tn on plain rows, but reproducible bit for bit:
+    the splits of the contraction go through the float32 workspace `ws` (gemm_tn_split_workspace elements) and are added in a fixed order."""
+    Mk, I, J = B.shape[0], A.shape[1], B.shape[1]
+    call("ocr_gemm_tn_split_bf16", ptr(_dev(A)), A.stride(0), ptr(B), B.stride(0), ptr(out), out.stride(0), Mk, I, J, float(scale),
+         ptr(colsum), ptr(ws), ws.numel(), _st())
+    return out
+
+
 def gemm_tn_batched(A, lda, strideA, B, ldb, strideB, out, ldo, strideOut, Mk, I, J, nbatch, colsum=None, strideColsum=0,
                     scale=1.0, splits=0):
     """nbatch independent out_b[I][J] += scale * A_b^T B_b in one launch (element strides between the problems)."""

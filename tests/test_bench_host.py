@@ -76,3 +76,35 @@ def test_counter_summary_divides_busy_cycles_by_the_kernels_own_cycles(tmp_path)
     assert abs(ws["mfma_busy_frac_grbm_window"] - 2.0e7 / (1024.0 * 8.0e5 / 8.0)) < 1e-12
     assert abs(ws["read_mb"] - 2.0 * 1000.0 * 1024 / 1e6) < 1e-9                      # FETCH_SIZE in KB, doubled (gfx950 correction)
     assert "mfma_busy_frac_own_cycles" not in k["_Z18adam_update_kernelPfPKfS_S_lffffPdllf"]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: loss as float64, parameters and gradients as float32; an array larger than its share of the budget is written as a
+    fixed seeded sample with its indices, the same sample from run to run."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    class Eng:
+        params = torch.arange(5000, dtype=torch.float32)
+        grads = -torch.arange(5000, dtype=torch.float32)
+        last_ctc, last_reg, last_gnorm = 1.5, 0.25, 3.0
+
+    b.dump_outputs(Eng, str(tmp_path / "a"), 1.75)
+    loss = np.load(str(tmp_path / "a" / "loss.npy"))
+    assert loss.dtype == np.float64 and loss.tolist() == [1.75, 1.5, 0.25, 3.0]
+    for name, sign in (("params", 1), ("grads", -1)):
+        got = np.load(str(tmp_path / "a" / ("%s.npy" % name)))
+        assert got.dtype == np.float32 and np.array_equal(got, sign * np.arange(5000, dtype=np.float32))
+        assert not (tmp_path / "a" / ("%s_index.npy" % name)).exists()
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 4096 + 2 * 12 * 1000)          # room for 1000 of the 5000 elements per array
+    for d in ("b", "c"):
+        b.dump_outputs(Eng, str(tmp_path / d), 1.75)
+    total = sum(f.stat().st_size for f in (tmp_path / "b").iterdir())
+    assert total <= b.DUMP_BUDGET_BYTES + 4 * 128                              # (+ the .npy headers)
+    for name, sign in (("params", 1), ("grads", -1)):
+        idx = np.load(str(tmp_path / "b" / ("%s_index.npy" % name)))
+        got = np.load(str(tmp_path / "b" / ("%s.npy" % name)))
+        assert idx.dtype == np.int64 and len(idx) == 1000 and np.all(np.diff(idx) > 0)
+        assert got.dtype == np.float32 and np.array_equal(got, sign * idx.astype(np.float32))
+        assert np.array_equal(idx, np.load(str(tmp_path / "c" / ("%s_index.npy" % name))))

@@ -88,29 +88,6 @@ def test_reference_import_surface():
     assert accuracy_calculation([[1]], [[1], [2]], isPrint=False) == 0       # length mismatch -> 0 (training.py:27-29)
 
 
-def test_reference_cli_script_runs_against_this_lib(monkeypatch, tmp_path, capsys):
-    """Executes the reference's OWN lstm/train_net.py source (when the checkout is present) with this repo's lib/:
-    argument parsing, cfg merge, directory creation and network construction must all work; the final train_net call
-    is intercepted because this host has no GPU."""
-    ref = '/root/reference/lstm/train_net.py'
-    if not os.path.exists(ref):
-        pytest.skip('reference checkout not present')
-    import sys
-    import lib.lstm.train as lt
-    from lstm_ctc_ocr_amd.config import cfg
-    called = {}
-    monkeypatch.setattr(lt, 'train_net', lambda network, imgdb, **kw: called.update(net=network, kw=kw, db=imgdb))
-    monkeypatch.setitem(cfg, 'ROOT_DIR', str(tmp_path))
-    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'lstm', 'train_net.py')
-    monkeypatch.setattr(sys, 'argv', ['train_net.py', '--network=LSTM_train', '--cfg=' + os.path.join(os.path.dirname(here), 'lstm.yml'),
-                                      '--restore=0', '--iters', '5'])
-    src = open(ref).read()
-    exec(compile(src, here, 'exec'), {'__file__': here, '__name__': '__main__'})
-    assert called['kw']['max_iters'] == 5 and called['kw']['restore'] is False and called['db'].name == 'lstm_train'
-    assert type(called['net']).__name__ == 'LSTM_train'
-    assert os.path.isdir(os.path.join(str(tmp_path), 'output', 'lstm_ctc'))
-
-
 def test_flat_layout_buckets():
     """Flat parameter layout of the engine: one contiguous regularised range, late layers (>= 75 % of the parameters) on top."""
     from lstm_ctc_ocr_amd.layout import FlatLayout

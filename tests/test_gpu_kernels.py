@@ -409,6 +409,25 @@ def test_gemm_tn(dev, Mk, I, J):
     assert relerr(out.cpu(), 1.5 * (A.t() @ B)) < 1e-4
 
 
+@pytest.mark.parametrize("Mk,I,J", [(4032, 512, 64), (1216, 512, 64), (300, 72, 136), (1000, 256, 384)])
+def test_gemm_tn_split_is_reproducible(dev, Mk, I, J):
+    """The split-partial form (the FC weight gradient of the train step): += into non-zero outputs, the same bits from call to call."""
+    A = bf(gen((Mk, I), 1)); B = bf(gen((Mk, J), 2))
+    Ad, Bd = A.to(dev).to(BF), B.to(dev).to(BF)
+    ws = torch.empty(ops.gemm_tn_split_workspace(Mk, I, J), dtype=torch.float32, device=dev)
+    out0, cs0 = bf(gen((I, J), 3)), bf(gen((J,), 4))
+    got = []
+    for _ in range(3):
+        out, cs = out0.to(dev).clone(), cs0.to(dev).clone()
+        ops.gemm_tn_split(Ad, Bd, out, ws, colsum=cs, scale=0.5)
+        got.append((out.cpu(), cs.cpu()))
+    assert all(torch.equal(o, got[0][0]) and torch.equal(c, got[0][1]) for o, c in got[1:])
+    assert relerr(got[0][0], out0 + 0.5 * (A.t() @ B)) < 1e-4 and relerr(got[0][1], cs0 + 0.5 * B.sum(0)) < 1e-4
+    out = torch.zeros((I, J), dtype=torch.float32, device=dev)
+    ops.gemm_tn_split(Ad, Bd, out, ws)                             # without column sums
+    assert relerr(out.cpu(), A.t() @ B) < 1e-4
+
+
 def test_gemm_tn_batched_and_xh(dev):
     """Two weight-gradient products in one launch (the BiLSTM directions) and the [x | h_prev] operand builder."""
     Nb, T, D, U = 8, 21, 512, 256
