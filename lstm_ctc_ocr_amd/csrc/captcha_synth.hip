@@ -338,11 +338,7 @@ extern "C" int ocr_captcha_synth(const int* params, int n_images, int words_per_
     const int ccap = (canvas_cap + 15) & ~15, wcap = (width_cap + 15) & ~15;
     const int lds = SY_H * (ccap + wcap) + (SY_TAPS * 256 + 512) * 4;
     if (lds > 160 * 1024) return OCR_ERR_INVALID;
-    static int lds_set = 0;
-    if (lds > lds_set) {
-        if (hipFuncSetAttribute((const void*)captcha_synth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC;
-        lds_set = lds;
-    }
+    if (ocr_allow_lds<captcha_synth_kernel>(lds) != hipSuccess) return OCR_ERR_EXEC;
     SynthArgs a{params, words_per_image, max_glyphs, (const uint8_t*)atlas, stamp, n_stamp, (uint8_t*)out, W, ccap, wcap, out_h};
     captcha_synth_kernel<<<n_images, SY_NT, lds, (hipStream_t)stream>>>(a);
     OCR_CHECK_LAUNCH();

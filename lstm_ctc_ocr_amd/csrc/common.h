@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 #define OCR_WAVE 64
 
@@ -79,7 +80,8 @@ __device__ __forceinline__ void dma16_saddr(unsigned lds_dst, unsigned voff, con
 
 // Tuning knobs (tile policies, stage counts, ...): read from the environment only by `make EXPERIMENTS=1` builds — the A/B tools load that
 // library through OCR_NATIVE_LIB; the product library uses the measured defaults.  Kernel-selection knobs that the parity tests force
-// (OCR_CONV_K2 / OCR_CONV_K3 / OCR_K2_CFG / OCR_W9_PLANES / OCR_LSTM_PROTO / OCR_LSTM_ROWS) are read by both.
+// (OCR_CONV_K2 / OCR_CONV_K3 / OCR_K2_CFG / OCR_CONV_WS / OCR_W9_PLANES / OCR_LSTM_PROTO / OCR_LSTM_ROWS) are read by both.  The 3x3
+// convolution's knobs, of both kinds, are all read in one place: gemm.hip's read_conv_knobs().
 static inline const char* ocr_tune_env(const char* name) {
 #ifdef OCR_EXPERIMENTS
     return getenv(name);
@@ -101,3 +103,19 @@ __device__ __forceinline__ void ocr_clk_exit(long long* clk) {
     clk[4] += c - clk[0]; clk[5] += t - clk[1]; clk[6] += 1;
 }
 __host__ __device__ static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Lets KERNEL launch with `bytes` of dynamic LDS on the current device (hipFuncSetAttribute MaxDynamicSharedMemorySize): called before
+// every launch, it sets the attribute the first time a device needs that much for this kernel instance and is a load otherwise.
+#define OCR_MAX_DEVICES 64
+template <auto KERNEL>
+static inline hipError_t ocr_allow_lds(int bytes) {
+    static std::atomic<int> allowed[OCR_MAX_DEVICES];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= OCR_MAX_DEVICES) return hipErrorInvalidDevice;
+    int have = allowed[dev].load(std::memory_order_acquire);
+    if (bytes <= have) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+    while (have < bytes && !allowed[dev].compare_exchange_weak(have, bytes, std::memory_order_acq_rel)) {}
+    return hipSuccess;
+}

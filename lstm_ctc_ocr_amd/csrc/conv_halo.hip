@@ -13,9 +13,7 @@
 // zeros for the MFMA operand (4 v_cndmask per fragment).
 // Pipeline: weight tiles double-buffered (one step ahead), halo tiles double-buffered (one chunk ahead, issued at
 // tap 0 AFTER the weight DMA so the counted wait of tap 1 does not have to drain it), raw s_barrier per step.
-#include "common.h"
-#include <stdlib.h>
-#include <string.h>
+#include "conv_plan.h"
 
 enum { IGH_BIAS = 1, IGH_RELU = 2, IGH_MASK = 16, IGH_ACCUM = 64 /* out (bf16) += value: a data gradient added to what another consumer already delivered */ };
 
@@ -290,122 +288,24 @@ void conv_halo_kernel(HaloArgs g, int NRpad /* halo rows rounded up to 8 * NW */
 // (A variant on v_mfma_f32_32x32x16_bf16 — same tiles, 32-row fragments, row swizzle (r & 7) ^ ((r >> 3) & 1) — was written in round 2,
 // passed the parity tests on hardware in round 3 and measured 10-15 % SLOWER on every layer (profiles/r03a_conv_32x32x16.log): removed.)
 
-template <int BN, int NW, int ABL = 0, int RPW = 32, int FNV = 4>
-static int launch_halo_(const HaloArgs& g, hipStream_t stream) {
-    if (!g.P) return 1;                                  // plan query (ocr_conv3x3_kernel_choice): this file's kernels, nothing is launched
-    constexpr int BM = RPW * NW;
+template <int BN, int NW>
+static int run_halo(const HaloArgs& g, hipStream_t stream) {
+    constexpr int BM = 32 * NW;
     const int NR = BM + 2 * g.cH + 2;
     const int NRpad = (NR + 8 * NW) / (8 * NW) * (8 * NW);       // strictly greater than NR: the spare rows are the zero rows
     const int lds = 2 * NRpad * 128 + 2 * BN * 128;              // halo stages, weight stages
-    static int lds_set = 0;
-    if (lds > lds_set) {
-        if (hipFuncSetAttribute((const void*)conv_halo_kernel<BN, NW, ABL, RPW, FNV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-            return OCR_ERR_EXEC;
-        lds_set = lds;
-    }
-    int mt = (g.M + BM - 1) / BM, nt = (g.N + BN - 1) / BN;
-    conv_halo_kernel<BN, NW, ABL, RPW, FNV><<<mt * nt, 64 * NW, lds, stream>>>(g, NRpad);
+    if (ocr_allow_lds<conv_halo_kernel<BN, NW>>(lds) != hipSuccess) return OCR_ERR_EXEC;
+    const int mt = (g.M + BM - 1) / BM, nt = (g.N + BN - 1) / BN;
+    conv_halo_kernel<BN, NW><<<mt * nt, 64 * NW, lds, stream>>>(g, NRpad);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
-template <int BN, int NW>
-static int launch_halo(const HaloArgs& g, hipStream_t stream) {
-#ifdef OCR_EXPERIMENTS
-    static int abl = -1;                        // timing ablations for tools/halo_variants.py (OCR_HALO_ABL; results are wrong)
-    if (abl < 0) { const char* e = getenv("OCR_HALO_ABL"); abl = e ? atoi(e) : 0; }
-    if (abl == 1) return launch_halo_<BN, NW, 1>(g, stream);
-    if (abl == 2) return launch_halo_<BN, NW, 2>(g, stream);
-    if (abl == 5) return launch_halo_<BN, NW, 5>(g, stream);
-#endif
-    return launch_halo_<BN, NW, 0>(g, stream);
-}
-
-int k2_try_dispatch(const void* x, const void* wpack, void* y, int M, int W, int H, int Cin, int Cout, const float* bias,
-                    const void* mask, int flags, hipStream_t stream, void* pool, int pool_kind);
-int ws_try_dispatch(const void* x, const void* wpack, void* y, int M, int W, int H, int Cin, int Cout, const float* bias,
-                    const void* mask, int flags, hipStream_t stream, void* pool, int pool_kind);
-#define K2_DEFAULT 1            // on since the weight prefetch distance went from 2 to 3 steps (profiles/r03n: the step 1.415 against 1.440 ms, three
-                                // interleaved runs each; with distance 2 it was an opt-in: no faster (tile D) or 1.4 % slower (tiles A + D) in the step,
-                                // profiles/r03l_bench_conv_ab.log, although 8 % faster back to back, profiles/r03j_conv_k2_final.log)
-
-// -1 = shape not covered (caller falls back to igemm.hip / gemm.hip)
-int halo_try_dispatch(const void* x, const void* wpack, void* y, int M, int W, int H, int Cin, int Cout, const float* bias,
-                      const void* mask, int flags, hipStream_t stream, void* pool, int pool_kind) {
-    if ((Cin & 63) || (Cout & 3) || M < 1024 || H > 30) return -1;
-    if (flags & ~(IGH_BIAS | IGH_RELU | IGH_MASK | IGH_ACCUM)) return -1;
-    // seventh generation (conv_ws.hip: weights in registers, workgroups persistent over the pixel tiles) for the short-K layers it covers and
-    // chooses (Cin = 64 / 128 at H = 16 / 8 with at least two tiles per workgroup); A/B knob OCR_CONV_WS = 0 / 2 (never / every covered shape)
-    if (pool_kind < 3) {
-        const int rc = ws_try_dispatch(x, wpack, y, M, W, H, Cin, Cout, bias, mask, flags, stream, pool, pool_kind);
-        if (rc >= 0) return rc;
-    }
-    if (pool_kind >= 3) {    // batch-norm statistics from the epilogue (3: forward, `pool` = float partial rows; 4: backward sums of a masked data
-                             // gradient, `pool` = host K3BnBwd): the plane-layout kernels only
-        if (pool_kind > 4 || !pool || (flags & IGH_ACCUM) || (M & 255)) return -1;
-        if (pool_kind == 3 ? (flags & IGH_MASK) != 0 : !(flags & IGH_MASK)) return -1;
-        static int k2s = -1;
-        if (k2s < 0) { const char* e = getenv("OCR_CONV_K2"); k2s = e ? atoi(e) : K2_DEFAULT; }
-        return k2s ? k2_try_dispatch(x, wpack, y, M, W, H, Cin, Cout, bias, mask, flags, stream, pool, pool_kind) : -1;
-    }
-    if (pool_kind) {         // fused max-pool: ReLU epilogue without mask, even feature axis, 2 x 2 only for H in {4, 8, 16} and even W
-        if (!pool || (flags & (IGH_MASK | IGH_ACCUM)) || !(flags & IGH_RELU) || (H & 1) || (Cout & 3) || (Cout % 64 && Cout % 128)) return -1;
-        if (pool_kind == 2 && ((H != 4 && H != 8 && H != 16) || (W & 1))) return -1;
-        if (pool_kind != 1 && pool_kind != 2) return -1;
-        if (M % (pool_kind == 2 ? 2 * H : 2)) return -1;
-    }
-    // fifth generation (conv_k2.hip: 128 x 64 wave tiles through an in-workgroup K split, ping-pong K halves) where its tiles fill the
-    // chip; A/B knob OCR_CONV_K2 = 0 keeps every shape on this file's kernels
-    static int k2 = -1;
-    if (k2 < 0) { const char* e = getenv("OCR_CONV_K2"); k2 = e ? atoi(e) : K2_DEFAULT; }
-    if (k2) {
-        const int rc = k2_try_dispatch(x, wpack, y, M, W, H, Cin, Cout, bias, mask, flags, stream, pool, pool_kind);
-        if (rc >= 0) return rc;
-    }
-    // Tile choice.  128-pixel workgroups of 4 waves leave room for TWO workgroups per CU (80 KiB of LDS each): they drift out
-    // of phase, so one's MFMA burst covers the other's barrier / DMA-issue / LDS-read phase (+5-7 % where the grid then still
-    // has two workgroups for every CU).  Otherwise 256-pixel workgroups of 8 waves, one per CU.
-    static int nw = -1;                                  // A/B knob OCR_HALO_NW: 8 / 4 force one kind, unset = by grid size
-    if (nw < 0) { const char* e = ocr_tune_env("OCR_HALO_NW"); nw = e ? atoi(e) : 0; }
-    static int stag = -1, stag_bit = 32;                 // experiment knob OCR_HALO_STAGGER=units[,bit] (units of 64 clocks; default off)
-    if (stag < 0) { const char* e = ocr_tune_env("OCR_HALO_STAGGER"); stag = e ? atoi(e) : 0; const char* c = e ? strchr(e, ',') : nullptr; if (c) stag_bit = atoi(c + 1); if (stag < 0) stag = 0; }
-    static int prio = -1;
-    if (prio < 0) { const char* e = ocr_tune_env("OCR_HALO_PRIO"); prio = e ? atoi(e) : 1; }      // measured: 451 against 458 us over the ten launches
-    HaloArgs g = {(const bf16_t*)x, (const bf16_t*)wpack, M, Cout, Cin, W, H, (bf16_t*)y, bias, (const bf16_t*)mask, flags, (bf16_t*)pool, pool_kind, stag, stag_bit, prio};
-#ifdef OCR_EXPERIMENTS      // measured and rejected in round 2: dense = equal, wide = 27 % slower
-    static int dense = -1;                               // A/B knob OCR_HALO_DENSE=1: 8 waves per 128-pixel tile (4 waves per SIMD with two workgroups per CU)
-    if (dense < 0) { const char* e = getenv("OCR_HALO_DENSE"); dense = e ? atoi(e) : 0; }
-    if (dense && nw != 8) {
-        const int NRd = (128 + 2 * H + 2 + 64) / 64 * 64;
-        const long mt4 = (M + 127) / 128;
-        if (NRd / 64 == 3) {
-            if (Cout >= 128 && mt4 * ((Cout + 127) / 128) >= 448) return launch_halo_<128, 8, 0, 16>(g, stream);
-            if (!(pool_kind == 2 && H == 16)) return launch_halo_<64, 8, 0, 16>(g, stream);     // one fragment per wave: no partner fragment
-        }
-    }
-    static int wide = -1;                                // A/B knob OCR_HALO_WIDE=1: 64 x 128 wave tiles (128 pixels x 256 channels per 4-wave workgroup, one per CU)
-    if (wide < 0) { const char* e = getenv("OCR_HALO_WIDE"); wide = e ? atoi(e) : 0; }
-    if (wide && nw != 8 && Cout % 256 == 0) {
-        const int NRw = (128 + 2 * H + 2 + 32) / 32 * 32;
-        if ((NRw / 32 == 5 || NRw / 32 == 6) && (long)((M + 127) / 128) * (Cout / 256) >= 224)
-            return launch_halo_<256, 4, 0, 32, 8>(g, stream);
-    }
-#endif
-    if (nw != 8) {
-        const int NR = 128 + 2 * H + 2, NRp = (NR + 32) / 32 * 32;
-        const long mt4 = (M + 127) / 128;
-        if (NRp / 32 == 5 || NRp / 32 == 6) {                                // counted vmcnt literals exist for 5 and 6
-            if (Cout >= 128 && mt4 * ((Cout + 127) / 128) >= 448) return launch_halo<128, 4>(g, stream);
-            // otherwise the smallest tile: it has the most workgroups, and every alternative below leaves CUs idle (a 256-channel
-            // layer at M = 8192 is 256 workgroups here against 64 of the 8-wave 256 x 128 tile)
-            if (nw != 8) return launch_halo<64, 4>(g, stream);
-        } else if (nw == 4) return -1;
-    }
-    const int NRpad = (256 + 2 * H + 2 + 64) / 64 * 64;
-    if (NRpad / 64 != 5 && NRpad / 64 != 6) return -1;               // counted vmcnt literals exist for 5 and 6
-    const int mt = (M + 255) / 256;
-    if (Cout >= 128 && (long)mt * ((Cout + 127) / 128) >= 200) return launch_halo<128, 8>(g, stream);
-    if (Cout >= 128 && (long)mt * ((Cout + 63) / 64) < 256) return launch_halo<128, 8>(g, stream);
-    return launch_halo<64, 8>(g, stream);
+// tiles: BN channels x 32 * NW pixels (conv3x3_plan's plan_halo chooses)
+int launch_halo(const ConvPlan& p, const ConvOperands& o, hipStream_t stream) {
+    const HaloArgs g = {(const bf16_t*)o.x, (const bf16_t*)o.wpack, p.M, p.Cout, p.Cin, p.W, p.H, (bf16_t*)o.y, o.bias, (const bf16_t*)o.mask,
+                        p.flags, (bf16_t*)o.pool, p.epi_kind, p.stagger, p.stagger_bit, p.prio};
+    if (p.nw == 4) return p.bn == 128 ? run_halo<128, 4>(g, stream) : run_halo<64, 4>(g, stream);
+    return p.bn == 128 ? run_halo<128, 8>(g, stream) : run_halo<64, 8>(g, stream);
 }
 
 int k3_set_clock_debug(void* dbg);       // conv_k3.hip: the plane-layout kernels stamp the same block
@@ -414,11 +314,4 @@ extern "C" int ocr_conv_halo_clock_debug(void* dbg /* device int64[8] or NULL */
     long long* p = (long long*)dbg;
     if (k3_set_clock_debug(dbg) != OCR_OK || ws_set_clock_debug(dbg) != OCR_OK) return OCR_ERR_EXEC;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_halo_clk), &p, sizeof(p)) == hipSuccess ? OCR_OK : OCR_ERR_EXEC;
-}
-
-// does the halo kernel take this shape (so that its epilogue-only features — accumulate, fused pool — may be asked for)?
-bool halo_covers(long M, int W, int H, int Cin, int Cout) {
-    if ((Cin & 63) || (Cout & 3) || M < 1024 || M > 0x7fffffffL || H > 30 || H < 1) return false;
-    const int NR4 = (128 + 2 * H + 2 + 32) / 32 * 32, NR8 = (256 + 2 * H + 2 + 64) / 64 * 64;
-    return NR4 / 32 == 5 || NR4 / 32 == 6 || NR8 / 64 == 5 || NR8 / 64 == 6;
 }

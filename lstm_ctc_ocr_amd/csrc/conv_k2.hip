@@ -25,8 +25,7 @@
 // offset that advances per step, no per-step vector arithmetic (the flat-pointer form cost 150-260 issue cycles per piece in
 // conv_halo); rows that do not exist (n >= N, pixels outside [0, M), the zero rows behind the halo) carry an out-of-range lane
 // offset and arrive as zeros.
-#include "common.h"
-#include <stdlib.h>
+#include "conv_plan.h"
 #include <type_traits>
 
 enum { K2_BIAS = 1, K2_RELU = 2, K2_MASK = 16, K2_ACCUM = 64 };
@@ -407,94 +406,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 // tile configurations: A = 256 pixels x 128 channels (waves 2 x 2 x 2 K), D = 256 x 64 (4 x 1 x 2 K: layers whose 256 x 128 tiles would not
 // fill the chip); 512 x 64 and 128 x 128 were built and measured too (profiles/r03e / r03h_conv*.log): never faster than these two
-template <int FM, int BN, int NST = 4>
-static int launch_k2(const K2Args& g, hipStream_t stream) {
-    if (!g.P) return BN == 128 ? 2 : 3;                  // plan query (ocr_conv3x3_kernel_choice): nothing is launched
+template <int FM, int BN, int NST>
+static int run_k2(const K2Args& g, hipStream_t stream) {
     constexpr int BM = (4 / (BN / 64)) * FM * 16;
     const int NRpad = (BM + 2 * g.cH + 4 + 7) / 8 * 8;             // needed rows + two zero rows, in 8-row DMA pieces
-    int lds = 2 * NRpad * 128 + NST * BN * 128;                     // halo stages, weight stages (the K-half exchange reuses them)
-    if (lds > 163840 || lds < 8 * FM * 2048) return -1;
+    int lds = 2 * NRpad * 128 + NST * BN * 128;                     // halo stages, weight stages (the K-half exchange reuses them; conv3x3_plan
+                                                                    // checks that they fit)
 #ifdef OCR_EXPERIMENTS
-    if (lds + 10240 <= 163840) lds += 10240; else if (g.abl & 8) return -1;      // room for the stamps
+    if (lds + 10240 <= 163840) lds += 10240;                        // room for the stamps
 #endif
-    static int attr = 0;
-    if (lds > attr) {
-        if (hipFuncSetAttribute((const void*)conv_k2_kernel<FM, BN, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC;
-        attr = lds;
-    }
+    if (ocr_allow_lds<conv_k2_kernel<FM, BN, NST>>(lds) != hipSuccess) return OCR_ERR_EXEC;
     const int mt = (g.M + BM - 1) / BM, nt = (g.N + BN - 1) / BN;
     conv_k2_kernel<FM, BN, NST><<<mt * nt, 512, lds, stream>>>(g, NRpad);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
-// Which tile, if any?  A where its tiles fill the chip (>= 224), else D; layers with fewer than OCR_K2_MINSTEPS K steps (default 18)
-// stay on conv_halo: with 9 steps a tile is mostly prologue and epilogue, and conv_halo's two independent workgroups per CU overlap
-// those (measured: conv2 33 against 40 us; conv3_1 forward, 18 steps: 26.9 on conv_halo, 27.6 on conv_k2, 24.0 on conv_k3 — profiles/r03q).  OCR_K2_CFG = A / D forces one tile where it covers the shape.
-static int k2_choose(long M, int H, int Cin, int Cout, int minsteps_k3 = -1 /* >= 0: the step floor of conv_k3.hip instead of OCR_K2_MINSTEPS */) {
-    if ((Cin & 63) || (Cout & 63) || M < 4096 || H > 16 || H < 1) return 0;
-    if (M * Cin * 2 >= 0x7fffffffL || (long)Cout * 9 * Cin * 2 >= 0x7fffffffL) return 0;   // 32-bit descriptor offsets
-    static int force = -1, minsteps = -1, allow_a = -1, mintiles = -1;
-    if (mintiles < 0) { const char* e = ocr_tune_env("OCR_K2_MINTILES"); mintiles = e ? atoi(e) : 128; }
-    if (force < 0) { const char* e = getenv("OCR_K2_CFG"); force = (e && (e[0] == 'A' || e[0] == 'D')) ? e[0] : 0; }
-    if (minsteps < 0) { const char* e = ocr_tune_env("OCR_K2_MINSTEPS"); minsteps = e ? atoi(e) : 18; }
-    // OCR_K2_TILES = D keeps the dispatcher off tile A.  With prefetch distance 2 tile A was SLOWER than conv_halo inside the train step
-    // (1.461 against 1.435 ms, profiles/r03k) and 15-25 % slower behind a cache scrub (profiles/r03m) although 6 % faster when the same
-    // launch repeats back to back: one 8-wave workgroup per CU in lock step has nothing to run while a piece arrives late from HBM.
-    // With distance 3 (five weight stages) it is faster in all three settings (profiles/r03n: cold 474 against 504 us over the ten
-    // layers, hot 416 against 446, step 1.415 against 1.440 ms).
-    if (allow_a < 0) { const char* e = ocr_tune_env("OCR_K2_TILES"); allow_a = (e && e[0] == 'D') ? 0 : 1; }
-    // first a tile whose grid fills the chip (>= 224 workgroups: A, then D), else one that fills at least half of it (OCR_K2_MINTILES, 128:
-    // the small-batch layers of configs[4], 6090 -> 6513 images/s; for the headline net preferring A with 128 tiles over D with 256 cost
-    // 22 us per step, profiles/r03_final_a_* against r03y)
-    const char order[2] = {'A', 'D'};
-    for (int pass = 0; pass < 2; ++pass)
-        for (int i = 0; i < 2; ++i) {
-            const char c = order[i];
-            if (force && c != force) continue;
-            if (!force && c == 'A' && !allow_a) continue;
-            const int bn = c == 'A' ? 128 : 64;
-            if (Cout % bn) continue;
-            if (force) return c;
-            if (9 * (Cin / 64) < (minsteps_k3 >= 0 ? minsteps_k3 : minsteps)) return 0;
-            if ((M + 255) / 256 * (Cout / bn) >= (pass == 0 ? 224 : mintiles)) return c;
-        }
-    return 0;
-}
-
-int k3_try_dispatch(int tile, const void* x, const void* wpack, void* y, int M, int W, int H, int Cin, int Cout, const float* bias,
-                    const void* mask, int flags, hipStream_t stream, void* pool, int pool_kind);
-
-// -1 = shape not covered (caller falls back to conv_halo.hip)
-int k2_try_dispatch(const void* x, const void* wpack, void* y, int M, int W, int H, int Cin, int Cout, const float* bias,
-                    const void* mask, int flags, hipStream_t stream, void* pool, int pool_kind) {
-    if (flags & ~(K2_BIAS | K2_RELU | K2_MASK | K2_ACCUM)) return -1;
-    // sixth generation (conv_k3.hip: the same tiles with the halo stored as feature-row planes) where it covers the shape; its own step floor
-    // OCR_K3_MINSTEPS (default 18 like conv_k2: the 9-step conv2 forward is no faster on it than on conv_halo's two workgroups per CU —
-    // 34.0 against 33.6 us, 41 against 39.7 behind a cache scrub, profiles/r03t); A/B knob OCR_CONV_K3 = 0
-    static int k3 = -1, k3min = -1;
-    if (k3 < 0) { const char* e = getenv("OCR_CONV_K3"); k3 = e ? atoi(e) : 1; }
-    if (k3min < 0) { const char* e = ocr_tune_env("OCR_K3_MINSTEPS"); k3min = e ? atoi(e) : 18; }
-    if (k3) {
-        const int c3 = k2_choose(M, H, Cin, Cout, k3min);
-        if (c3) {
-            const int rc = k3_try_dispatch(c3, x, wpack, y, M, W, H, Cin, Cout, bias, mask, flags, stream, pool, pool_kind);
-            if (rc >= 0) return rc;
-        }
-    }
-    if (pool_kind >= 3) return -1;                       // batch-norm statistics in the epilogue: conv_k3 only
-    const int c = k2_choose(M, H, Cin, Cout);
-    if (!c) return -1;
-    static int abl = -1;
-    if (abl < 0) { const char* e = ocr_tune_env("OCR_K2_ABL"); abl = e ? atoi(e) : 0; }
-    K2Args g = {(const bf16_t*)x, (const bf16_t*)wpack, M, Cout, Cin, W, H, (bf16_t*)y, bias, (const bf16_t*)mask, flags, (bf16_t*)pool, pool_kind, abl};
+// tile and weight stages as conv3x3_plan chose them
+int launch_k2(const ConvPlan& p, const ConvOperands& o, hipStream_t stream) {
+    const K2Args g = {(const bf16_t*)o.x, (const bf16_t*)o.wpack, p.M, p.Cout, p.Cin, p.W, p.H, (bf16_t*)o.y, o.bias, (const bf16_t*)o.mask,
+                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.abl};
 #ifdef OCR_EXPERIMENTS
-    static int nst = -1;                                 // A/B knob OCR_K2_NST: weight stages (prefetch distance + 2)
-    if (nst < 0) { const char* e = ocr_tune_env("OCR_K2_NST"); nst = e ? atoi(e) : 0; }
-    if (c == 'A' && nst == 4) return launch_k2<8, 128, 4>(g, stream);
-    if (c == 'D' && nst == 5) return launch_k2<4, 64, 5>(g, stream);
-    if (c == 'D' && nst == 6) return launch_k2<4, 64, 6>(g, stream);
+    if (p.tile == 'A' && p.nst == 4) return run_k2<8, 128, 4>(g, stream);
+    if (p.tile == 'D' && p.nst == 5) return run_k2<4, 64, 5>(g, stream);
+    if (p.tile == 'D' && p.nst == 6) return run_k2<4, 64, 6>(g, stream);
 #endif
-    // tile A: five weight stages = prefetch distance 3 (see k2_choose); tile D: four — five or six change nothing for it (profiles/r03o)
-    if (c == 'A') return launch_k2<8, 128, 5>(g, stream);
-    return launch_k2<4, 64, 4>(g, stream);
+    if (p.tile == 'A') return run_k2<8, 128, 5>(g, stream);
+    return run_k2<4, 64, 4>(g, stream);
 }

@@ -27,8 +27,7 @@
 //     on that image (store phase 4.8 -> 2.8 us per launch, 8.9 -> 4.2 with the mask: profiles/r03u / r03v_k3_phases_*.log).
 // Covered: H in {4, 8, 16} with W % (256 / H) == 0; H in {2, 4, 8} with any W whose boundary rows fit the plane (GENW, see the template
 // parameter); M % 256 == 0, Cin % 64 == 0, Cout % 64 == 0; everything else stays on conv_k2 / conv_halo.
-#include "common.h"
-#include <stdlib.h>
+#include "conv_plan.h"
 #include <type_traits>
 
 enum { K3_BIAS = 1, K3_RELU = 2, K3_MASK = 16, K3_ACCUM = 64 };
@@ -45,8 +44,6 @@ struct K3Args {
     // the partial sums of the batch-norm BACKWARD pass per tile: [M / 256][2][N] = (sum g, sum g * xhat), xhat = (bnz - bn_mean) * bn_rstd
     const bf16_t* bnz; const float* bn_mean; const float* bn_rstd;
 };
-// what `pool` points to (HOST memory) when k3_try_dispatch is called with pool_kind 4
-struct K3BnBwd { float* partials; const void* z; const float* mean; const float* rstd; };
 
 #ifdef OCR_EXPERIMENTS
 // diagnostic (experiments build): wall-clock stamps (100 MHz) of every workgroup's first thread — dbg[block * 8 + {0 entry, 1 prologue landed,
@@ -492,96 +489,60 @@ template <int FM, int BN, int NST, int H, bool GENW>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_k3b_kernel(K3Args g) { k3_body<FM, BN, NST, H, false, GENW, true>(g); }
 
 template <int FM, int BN, int NST, int H, bool GENW>
-static int launch_k3b(const K3Args& g, hipStream_t stream) {
-    if (!g.P) return (GENW ? 6 : 4) + (BN == 128 ? 0 : 1);
+static int run_k3b(const K3Args& g, hipStream_t stream) {
     constexpr int PS = (256 / H + 2 + 7) / 8 * 8, PPIECES = (H * PS / 8 + 7) / 8 * 8;
     constexpr int need = NST * BN * 128 + 2 * PPIECES * 1024, xch = 8 * (FM / 2) * 4 * 1024, lds = need > xch ? need : xch;
     static_assert(lds <= 163840 && 256 * BN * 2 + 2 * (512 / (BN / 8)) * BN * 4 <= lds, "LDS");
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_k3b_kernel<FM, BN, NST, H, GENW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC;
-        attr = true;
-    }
+    if (ocr_allow_lds<conv_k3b_kernel<FM, BN, NST, H, GENW>>(lds) != hipSuccess) return OCR_ERR_EXEC;
     conv_k3b_kernel<FM, BN, NST, H, GENW><<<(g.M / 256) * ((g.N + BN - 1) / BN), 512, lds, stream>>>(g);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
 
 template <int FM, int BN, int NST, int H, bool SINGLE = false, bool GENW = false>
-static int launch_k3(const K3Args& g, hipStream_t stream) {
-    if (!g.P) return (GENW ? 6 : 4) + (BN == 128 ? 0 : 1);       // plan query (ocr_conv3x3_kernel_choice): nothing is launched
+static int run_k3(const K3Args& g, hipStream_t stream) {
     constexpr int PS = (256 / H + 2 + 7) / 8 * 8, PPIECES = (H * PS / 8 + 7) / 8 * 8;
     constexpr int need = NST * BN * 128 + (SINGLE ? 1 : 2) * PPIECES * 1024;     // weight stages, padded halo buffer(s)
     constexpr int xch = 8 * (FM / 2) * 4 * 1024;                                  // the K-half exchange reuses them
     constexpr int lds = need > xch ? need : xch;
     static_assert(lds <= 163840, "LDS");
     static_assert(256 * BN * 2 + 2 * (512 / (BN / 8)) * BN * 4 <= lds, "staged image + the statistics scratch behind it");
-    static bool attr = false;
     const int mt = g.M / 256, nt = (g.N + BN - 1) / BN;
     if constexpr (GENW) {
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)conv_k3w_kernel<FM, BN, NST, H>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC;
-            attr = true;
-        }
+        if (ocr_allow_lds<conv_k3w_kernel<FM, BN, NST, H>>(lds) != hipSuccess) return OCR_ERR_EXEC;
         conv_k3w_kernel<FM, BN, NST, H><<<mt * nt, 512, lds, stream>>>(g);
     } else {
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)conv_k3_kernel<FM, BN, NST, H, SINGLE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC;
-            attr = true;
-        }
+        if (ocr_allow_lds<conv_k3_kernel<FM, BN, NST, H, SINGLE>>(lds) != hipSuccess) return OCR_ERR_EXEC;
         conv_k3_kernel<FM, BN, NST, H, SINGLE><<<mt * nt, 512, lds, stream>>>(g);
     }
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
 
-// -1 = shape not covered.  tile: 'A' = 256 pixels x 128 channels, 'D' = 256 x 64 (chosen by conv_k2.hip's k2_choose)
-int k3_try_dispatch(int tile, const void* x, const void* wpack, void* y, int M, int W, int H, int Cin, int Cout, const float* bias,
-                    const void* mask, int flags, hipStream_t stream, void* pool, int pool_kind) {
-    if (H != 2 && H != 4 && H != 8 && H != 16) return -1;
-    if (M % 256 || (Cin & 63) || (Cout & 63)) return -1;
-    const int NC = 256 / H, PS = (NC + 2 + 7) / 8 * 8;
-    const bool genw = W % NC != 0;                       // tiles cross image boundaries: the general-width form (one zero row per boundary)
-    if (genw && (H == 16 || NC + 2 + (NC + W - 1) / W > PS)) return -1;       // (H = 16: 16-column tiles, W >= 16 there — not instantiated)
-    if (H == 2 && (!genw || (pool_kind && pool_kind < 3))) return -1;       // H = 2 exists in the general-width form only (128-column tiles)
-    if (pool_kind >= 3 && (flags & K3_ACCUM)) return -1; // statistics are taken in the staged write-out
-    if (pool_kind == 4 && !(flags & K3_MASK)) return -1;  // batch-norm backward sums: of the ReLU-masked gradient
-    static int genw_on = -1;                             // A/B knob OCR_K3_GENW = 0: general-width shapes stay on conv_k2 / conv_halo
-    if (genw_on < 0) { const char* e = ocr_tune_env("OCR_K3_GENW"); genw_on = e ? atoi(e) : 1; }
-    if (genw && !genw_on) return -1;
-    static int prio = -1;
-    if (prio < 0) { const char* e = ocr_tune_env("OCR_K3_PRIO"); prio = e ? atoi(e) : 2; }      // measured: 1 (equal) 349 us, 2 322, 3 324 over the ten layers (profiles/r03af)
-    K3Args g = {(const bf16_t*)x, (const bf16_t*)wpack, M, Cout, Cin, W, H, (bf16_t*)y, bias, (const bf16_t*)mask, flags, (bf16_t*)pool, pool_kind, prio,
-                nullptr, nullptr, nullptr};
-    if (pool_kind == 4 && x) {                           // (plan queries pass no operands)
-        const K3BnBwd* e = (const K3BnBwd*)pool;
-        g.pool = (bf16_t*)e->partials; g.bnz = (const bf16_t*)e->z; g.bn_mean = e->mean; g.bn_rstd = e->rstd;
-    }
-    const bool single = Cin == 64;
-    if (pool_kind == 4) {                                // instances exist for the shapes batch-norm layers have here: H in {4, 8}, several chunks
-        if (single || (H != 4 && H != 8)) return -1;
-        if (tile == 'A') {
-            if (Cout % 128) return -1;
-            if (genw) return H == 4 ? launch_k3b<8, 128, 5, 4, true>(g, stream) : launch_k3b<8, 128, 5, 8, true>(g, stream);
-            return H == 4 ? launch_k3b<8, 128, 5, 4, false>(g, stream) : launch_k3b<8, 128, 5, 8, false>(g, stream);
+// the instances: tile 'A' = 256 pixels x 128 channels, 'D' = 256 x 64; H and the forms as conv3x3_plan's plan_k3 chose them
+int launch_k3(const ConvPlan& p, const ConvOperands& o, hipStream_t stream) {
+    const K3Args g = {(const bf16_t*)o.x, (const bf16_t*)o.wpack, p.M, p.Cout, p.Cin, p.W, p.H, (bf16_t*)o.y, o.bias, (const bf16_t*)o.mask,
+                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.prio, (const bf16_t*)o.bnz, o.bn_mean, o.bn_rstd};
+    const int H = p.H;
+    const bool A = p.tile == 'A';
+    if (p.epi_kind == CONV_EPI_BNBWD) {
+        if (A) {
+            if (p.genw) return H == 4 ? run_k3b<8, 128, 5, 4, true>(g, stream) : run_k3b<8, 128, 5, 8, true>(g, stream);
+            return H == 4 ? run_k3b<8, 128, 5, 4, false>(g, stream) : run_k3b<8, 128, 5, 8, false>(g, stream);
         }
-        if (genw) return H == 4 ? launch_k3b<4, 64, 4, 4, true>(g, stream) : launch_k3b<4, 64, 4, 8, true>(g, stream);
-        return H == 4 ? launch_k3b<4, 64, 4, 4, false>(g, stream) : launch_k3b<4, 64, 4, 8, false>(g, stream);
+        if (p.genw) return H == 4 ? run_k3b<4, 64, 4, 4, true>(g, stream) : run_k3b<4, 64, 4, 8, true>(g, stream);
+        return H == 4 ? run_k3b<4, 64, 4, 4, false>(g, stream) : run_k3b<4, 64, 4, 8, false>(g, stream);
     }
-    if (genw) {
-        if (tile == 'A') {
-            if (Cout % 128) return -1;
-            return H == 2 ? launch_k3<8, 128, 5, 2, false, true>(g, stream) : H == 4 ? launch_k3<8, 128, 5, 4, false, true>(g, stream)
-                                                                                      : launch_k3<8, 128, 5, 8, false, true>(g, stream);
-        }
-        return H == 2 ? launch_k3<4, 64, 4, 2, false, true>(g, stream) : H == 4 ? launch_k3<4, 64, 4, 4, false, true>(g, stream)
-                                                                                  : launch_k3<4, 64, 4, 8, false, true>(g, stream);
+    if (p.genw) {
+        if (A) return H == 2 ? run_k3<8, 128, 5, 2, false, true>(g, stream) : H == 4 ? run_k3<8, 128, 5, 4, false, true>(g, stream)
+                                                                                   : run_k3<8, 128, 5, 8, false, true>(g, stream);
+        return H == 2 ? run_k3<4, 64, 4, 2, false, true>(g, stream) : H == 4 ? run_k3<4, 64, 4, 4, false, true>(g, stream)
+                                                                               : run_k3<4, 64, 4, 8, false, true>(g, stream);
     }
-    if (tile == 'A') {
-        if (Cout % 128) return -1;
-        if (H == 16) return single ? launch_k3<8, 128, 5, 16, true>(g, stream) : launch_k3<8, 128, 4, 16>(g, stream);     // 2 x 48 KiB of halo: four stages
-        return H == 4 ? launch_k3<8, 128, 5, 4>(g, stream) : launch_k3<8, 128, 5, 8>(g, stream);
+    if (A) {
+        if (H == 16) return p.single ? run_k3<8, 128, 5, 16, true>(g, stream) : run_k3<8, 128, 4, 16>(g, stream);     // 2 x 48 KiB of halo: four stages
+        return H == 4 ? run_k3<8, 128, 5, 4>(g, stream) : run_k3<8, 128, 5, 8>(g, stream);
     }
-    if (H == 16) return single ? launch_k3<4, 64, 4, 16, true>(g, stream) : launch_k3<4, 64, 4, 16>(g, stream);
-    return H == 4 ? launch_k3<4, 64, 4, 4>(g, stream) : launch_k3<4, 64, 4, 8>(g, stream);
+    if (H == 16) return p.single ? run_k3<4, 64, 4, 16, true>(g, stream) : run_k3<4, 64, 4, 16>(g, stream);
+    return H == 4 ? run_k3<4, 64, 4, 4>(g, stream) : run_k3<4, 64, 4, 8>(g, stream);
 }

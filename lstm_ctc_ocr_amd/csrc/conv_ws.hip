@@ -23,8 +23,7 @@
 // fragment is CF = min(16, columns) consecutive image columns x 16 / CF feature rows.
 // Covered: (H, Cin) in {(16, 64), (16, 128), (8, 128)}, Cout % 64 == 0, W % columns-per-tile == 0, bias / ReLU / ReLU-mask write-outs and the
 // fused 1 x 2 / 2 x 2 max-pool; everything else stays on conv_k3 / conv_k2 / conv_halo.
-#include "common.h"
-#include <stdlib.h>
+#include "conv_plan.h"
 #include <type_traits>
 
 enum { WS_BIAS = 1, WS_RELU = 2, WS_MASK = 16, WS_ACCUM = 64 };
@@ -420,64 +419,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 template <int H, int NC, int KSPLIT, bool MASK>
-static int launch_ws_(WsArgs& g, int grid, hipStream_t stream) {
+static int launch_ws_(const WsArgs& g, int grid, hipStream_t stream) {
     using G = WsCfg<H, NC, KSPLIT>;
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_ws_kernel<H, NC, KSPLIT, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, MASK ? G::LDS_MASK : G::LDS_PLAIN) != hipSuccess) return OCR_ERR_EXEC;
-        attr = true;
-    }
-    conv_ws_kernel<H, NC, KSPLIT, MASK><<<grid, 256, MASK ? G::LDS_MASK : G::LDS_PLAIN, stream>>>(g);
+    constexpr int lds = MASK ? G::LDS_MASK : G::LDS_PLAIN;
+    if (ocr_allow_lds<conv_ws_kernel<H, NC, KSPLIT, MASK>>(lds) != hipSuccess) return OCR_ERR_EXEC;
+    conv_ws_kernel<H, NC, KSPLIT, MASK><<<grid, 256, lds, stream>>>(g);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
 template <int H, int NC, int KSPLIT>
-static int launch_ws(WsArgs& g, int cus, hipStream_t stream) {
-    using G = WsCfg<H, NC, KSPLIT>;
-    if (!g.P) return 8;                                  // plan query (ocr_conv3x3_kernel_choice): nothing is launched
-    const int mtiles = g.M / G::BM;
-    g.ntiles = g.N / 64;
-    int slots = cus / g.ntiles;
-    if (slots < 1) slots = 1;
-    if (slots > mtiles) slots = mtiles;
-    g.per_slot = (mtiles + slots - 1) / slots;
-    slots = (mtiles + g.per_slot - 1) / g.per_slot;      // no idle workgroups behind the last tile
-    g.slots = slots;
-    const int grid = slots * g.ntiles;
-    g.xcd_map = (grid % 8 == 0 && (grid / 8) % g.ntiles == 0) ? 1 : 0;
+static int launch_ws(const WsArgs& g, int grid, hipStream_t stream) {
     return (g.flags & WS_MASK) ? launch_ws_<H, NC, KSPLIT, true>(g, grid, stream) : launch_ws_<H, NC, KSPLIT, false>(g, grid, stream);
 }
-
-// -1 = shape not covered / not chosen (the caller goes on to conv_k3 / conv_k2 / conv_halo).
-// OCR_CONV_WS: 0 never, 1 (default) where a workgroup gets at least two tiles, 2 every covered shape (parity tests at small sizes)
-int ws_try_dispatch(const void* x, const void* wpack, void* y, int M, int W, int H, int Cin, int Cout, const float* bias,
-                    const void* mask, int flags, hipStream_t stream, void* pool, int pool_kind) {
-    static int mode = -1, cus = 0;
-    if (mode < 0) { const char* e = getenv("OCR_CONV_WS"); mode = e ? atoi(e) : 1; }
-    if (!mode) return -1;
-    if (flags & ~(WS_BIAS | WS_RELU | WS_MASK)) return -1;
-    if (pool_kind < 0 || pool_kind > 2 || (pool_kind && (!(flags & WS_RELU) || (flags & WS_MASK)))) return -1;
-    if ((Cout & 63) || (long)M * Cin * 2 > 0x7fffffffL || (long)M * Cout * 2 > 0x7fffffffL) return -1;
-    int nc, bm;
-    if (H == 16 && Cin == 64) { nc = 16; bm = 256; }
-    else if (H == 16 && Cin == 128) { nc = 8; bm = 128; }
-    else if (H == 8 && Cin == 128) { nc = 16; bm = 128; }
-    else return -1;
-    if (W % nc || M % bm) return -1;
-    if (pool_kind == 2 && (W & 1)) return -1;
-    // CU count of the device: latched only once the query SUCCEEDED (the host-only plan queries of the lowering — x == nullptr, possibly
-    // no device at all — came first and fixed the 256 fallback for the rest of the process); until then every call asks again
-    if (!cus) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    }
-    const int ncu = cus > 0 ? cus : 256;                 // no device visible (CPU-only policy tests): the MI355X's count
-    // default policy (measured, profiles/r05e_ws_bench.log): the single-chunk instance (Cin = 64: conv2 forward 40.8 -> 32.3 us) from two tiles
-    // per workgroup on; the K-split instances (Cin = 128) are correct but lose to conv_k3 (conv2 data gradient 35 against 28 us, conv3_1 forward
-    // 32 against 21: their per-workgroup weight hand-round costs 7-8 us of a 4-tile run) — OCR_CONV_WS=2 runs them for the parity tests
-    if (mode == 1 && (Cin != 64 || (long)(M / bm) * (Cout / 64) < 2L * ncu)) return -1;
-    WsArgs g = {(const bf16_t*)x, (const bf16_t*)wpack, M, Cout, Cin, W, H, (bf16_t*)y, bias, (const bf16_t*)mask, flags, (bf16_t*)pool, pool_kind, 0, 0, 0, 0};
-    if (H == 16 && Cin == 64) return launch_ws<16, 16, 1>(g, ncu, stream);
-    if (H == 16) return launch_ws<16, 8, 2>(g, ncu, stream);
-    return launch_ws<8, 16, 2>(g, ncu, stream);
+// instances: (H, Cin) = (16, 64), (16, 128), (8, 128); conv3x3_plan's plan_ws chooses them and sizes the persistent grid
+int launch_ws(const ConvPlan& p, const ConvOperands& o, hipStream_t stream) {
+    const WsArgs g = {(const bf16_t*)o.x, (const bf16_t*)o.wpack, p.M, p.Cout, p.Cin, p.W, p.H, (bf16_t*)o.y, o.bias, (const bf16_t*)o.mask,
+                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.Cout / 64, p.slots, p.per_slot, p.xcd_map};
+    if (p.H == 16 && p.ws_ksplit == 1) return launch_ws<16, 16, 1>(g, p.grid, stream);
+    if (p.H == 16) return launch_ws<16, 8, 2>(g, p.grid, stream);
+    return launch_ws<8, 16, 2>(g, p.grid, stream);
 }

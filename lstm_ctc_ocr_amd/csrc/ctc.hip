@@ -475,9 +475,7 @@ extern "C" int ocr_set_ctc_engine(int fast) { g_ctc_fast = fast; return OCR_OK; 
 // variable-width workload: 65 KiB); the limit is raised once
 constexpr size_t CTC_FAST_LDS_MAX = 128 * 1024;
 static bool ctc_fast_allow_lds() {
-    static int ok = -1;
-    if (ok < 0) ok = hipFuncSetAttribute((const void*)ctc_fast_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CTC_FAST_LDS_MAX) == hipSuccess;
-    return ok == 1;
+    return ocr_allow_lds<ctc_fast_kernel>((int)CTC_FAST_LDS_MAX) == hipSuccess;
 }
 
 extern "C" int ocr_ctc_workspace_size(int max_label_len, int max_time, int minibatch,

@@ -262,12 +262,7 @@ extern "C" int ocr_ctc_beam_decode(const float* activations, const int* input_le
     a.node_slot = a.node_parent + (size_t)minibatch * pool;
     a.node_label = (short*)(a.node_slot + (size_t)minibatch * pool);
     const size_t lds = beam_lds_bytes(alphabet_size, beam_width);
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-        if (hipFuncSetAttribute((const void*)ctc_beam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return OCR_ERR_EXEC;
-        lds_set = lds;
-    }
+    if (ocr_allow_lds<ctc_beam_kernel>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
     ctc_beam_kernel<<<minibatch, 256, lds, stream>>>(a);
     OCR_CHECK_LAUNCH();
     return OCR_OK;

@@ -336,21 +336,20 @@ int tn2_try_dispatch(const void* A, long lda, const void* B, long ldb, float* ou
     const int km = pair ? 2 : mode;
     dim3 grid((unsigned)(tiles * splits));          // empty splits (kbeg >= Mk) return at once
 #define TN2_LAUNCH(M_, BK_, NS_) do { \
-        static bool attr = false; const int lds = NS_ * 2 * BK_ * 256; \
-        if (!attr) { if (hipFuncSetAttribute((const void*)gemm_tn2_kernel<M_, BK_, NS_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC; attr = true; } \
+        const int lds = NS_ * 2 * BK_ * 256; \
+        if (ocr_allow_lds<gemm_tn2_kernel<M_, BK_, NS_>>(lds) != hipSuccess) return OCR_ERR_EXEC; \
         gemm_tn2_kernel<M_, BK_, NS_><<<grid, 256, lds, stream>>>(g); } while (0)
 #define TN2_MODE(BK_, NS_) do { if (km == 2) TN2_LAUNCH(2, BK_, NS_); else if (km == 1) TN2_LAUNCH(1, BK_, NS_); else TN2_LAUNCH(0, BK_, NS_); } while (0)
     if (wide) {                                    // 8 waves, 64-row stages x 2 (or x 3 with OCR_TN2_PIPE=3)
-        static bool attr8[3] = {false, false, false};
         const int ns = cfg == 4 ? 4 : (cfg == 3 ? 3 : 2), lds = ns * 2 * 64 * 256;
         if (ns == 4) {
-            if (!attr8[2]) { if (hipFuncSetAttribute((const void*)gemm_tn2_kernel<0, 64, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC; attr8[2] = true; }
+            if (ocr_allow_lds<gemm_tn2_kernel<0, 64, 4, 8>>(lds) != hipSuccess) return OCR_ERR_EXEC;
             gemm_tn2_kernel<0, 64, 4, 8><<<grid, 512, lds, stream>>>(g);
         } else if (ns == 3) {
-            if (!attr8[1]) { if (hipFuncSetAttribute((const void*)gemm_tn2_kernel<0, 64, 3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC; attr8[1] = true; }
+            if (ocr_allow_lds<gemm_tn2_kernel<0, 64, 3, 8>>(lds) != hipSuccess) return OCR_ERR_EXEC;
             gemm_tn2_kernel<0, 64, 3, 8><<<grid, 512, lds, stream>>>(g);
         } else {
-            if (!attr8[0]) { if (hipFuncSetAttribute((const void*)gemm_tn2_kernel<0, 64, 2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC; attr8[0] = true; }
+            if (ocr_allow_lds<gemm_tn2_kernel<0, 64, 2, 8>>(lds) != hipSuccess) return OCR_ERR_EXEC;
             gemm_tn2_kernel<0, 64, 2, 8><<<grid, 512, lds, stream>>>(g);
         }
     }

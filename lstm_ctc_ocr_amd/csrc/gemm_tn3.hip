@@ -285,13 +285,12 @@ extern "C" int ocr_gemm_tn_jobs_bf16(const void* jobs, int njobs, void* stream) 
     const int t1 = njobs > 1 ? (j[1].I >> 7) * (j[1].J >> 7) * j[1].nbatch : 0;
     static int nst = -1;                             // kernel-selection knob OCR_TN3_NST: 4 stages (prefetch distance 2) / 5 (distance 3, all 160 KiB of LDS)
     if (nst < 0) { const char* e = getenv("OCR_TN3_NST"); nst = (e && atoi(e) == 5) ? 5 : 4; }      // measured equal (profiles/r04d: 1.2682 / 1.2681 ms per step): 4
-    static bool attr[2] = {false, false};
     const int lds = nst * 2 * 64 * 256;              // stages x (A tile | B tile); the K-half exchange (64 KiB) reuses them
     if (nst == 4) {
-        if (!attr[0]) { if (hipFuncSetAttribute((const void*)gemm_tn3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC; attr[0] = true; }
+        if (ocr_allow_lds<gemm_tn3_kernel<4>>(lds) != hipSuccess) return OCR_ERR_EXEC;
         gemm_tn3_kernel<4><<<t0 + t1, 512, lds, (hipStream_t)stream>>>(j[0], njobs > 1 ? j[1] : j[0], t0);
     } else {
-        if (!attr[1]) { if (hipFuncSetAttribute((const void*)gemm_tn3_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return OCR_ERR_EXEC; attr[1] = true; }
+        if (ocr_allow_lds<gemm_tn3_kernel<5>>(lds) != hipSuccess) return OCR_ERR_EXEC;
         gemm_tn3_kernel<5><<<t0 + t1, 512, lds, (hipStream_t)stream>>>(j[0], njobs > 1 ? j[1] : j[0], t0);
     }
     OCR_CHECK_LAUNCH();

@@ -232,12 +232,7 @@ template <int BN, int MODE, int STAGES, int NW>
 static int launch_ig2(const IgArgs& g, hipStream_t stream) {
     constexpr int BM = 32 * NW;
     constexpr int LDS = STAGES * (BM * 128 + BN * 128);
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)igemm_kernel<BN, MODE, STAGES, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-            return OCR_ERR_EXEC;
-        attr_set = true;
-    }
+    if (ocr_allow_lds<igemm_kernel<BN, MODE, STAGES, NW>>(LDS) != hipSuccess) return OCR_ERR_EXEC;
     int mt = (g.M + BM - 1) / BM, nt = (g.N + BN - 1) / BN;
     igemm_kernel<BN, MODE, STAGES, NW><<<mt * nt, 64 * NW, LDS, stream>>>(g);
     OCR_CHECK_LAUNCH();

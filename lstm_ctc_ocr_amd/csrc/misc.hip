@@ -81,11 +81,7 @@ __global__ void occupy_kernel(long long ticks, int* __restrict__ sink) {
 }
 extern "C" int ocr_occupy_cus(int nblocks, int threads, int lds_bytes, float us, void* stream) {
     if (nblocks <= 0 || nblocks > 1024 || threads <= 0 || threads > 1024 || lds_bytes < 0 || lds_bytes > 160 * 1024 || !(us >= 0.f) || us > 1e5f) return OCR_ERR_INVALID;
-    static int attr = 0;
-    if (lds_bytes > attr) {
-        if (hipFuncSetAttribute((const void*)occupy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return OCR_ERR_EXEC;
-        attr = 160 * 1024;
-    }
+    if (ocr_allow_lds<occupy_kernel>(lds_bytes) != hipSuccess) return OCR_ERR_EXEC;
     occupy_kernel<<<nblocks, threads, lds_bytes, (hipStream_t)stream>>>((long long)(us * 100.0f), nullptr);
     OCR_CHECK_LAUNCH();
     return OCR_OK;

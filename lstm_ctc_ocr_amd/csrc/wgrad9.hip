@@ -1176,12 +1176,10 @@ int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, 
     g.cs_part = dbias ? g.part + (size_t)p.S * 9 * Cin * Cout : nullptr;
     const int grid = p.S * p.T_ci * p.T_co;
 #define W9_LAUNCH(LA_, AT_, DBG_, ...) do { \
-        static bool attr = false; \
-        if (!attr) { if (hipFuncSetAttribute((const void*)wgrad9_kernel<LA_, AT_, DBG_, ##__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, W9_LDS) != hipSuccess) return OCR_ERR_EXEC; attr = true; } \
+        if (ocr_allow_lds<wgrad9_kernel<LA_, AT_, DBG_, ##__VA_ARGS__>>(W9_LDS) != hipSuccess) return OCR_ERR_EXEC; \
         wgrad9_kernel<LA_, AT_, DBG_, ##__VA_ARGS__><<<grid, 512, W9_LDS, stream>>>(g); } while (0)
 #define W9C_LAUNCH(LA_, NS_, NB_, DBG_) do { \
-        static bool attr = false; \
-        if (!attr) { if (hipFuncSetAttribute((const void*)wgrad9c_kernel<LA_, NS_, NB_, DBG_>, hipFuncAttributeMaxDynamicSharedMemorySize, W9_LDS) != hipSuccess) return OCR_ERR_EXEC; attr = true; } \
+        if (ocr_allow_lds<wgrad9c_kernel<LA_, NS_, NB_, DBG_>>(W9_LDS) != hipSuccess) return OCR_ERR_EXEC; \
         wgrad9c_kernel<LA_, NS_, NB_, DBG_><<<grid, 512, W9_LDS, stream>>>(g); } while (0)
     // plane-layout kernel where it covers the shape (A/B knob OCR_W9_PLANES = 0: wgrad9_kernel everywhere)
     static int planes = -1;
@@ -1195,8 +1193,7 @@ int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, 
     if (use_p) {
         // (look-ahead 3 and 4 of the fragment read stream measured equal to 2: profiles/r03s_wgrad9p.log)
 #define W9P_LAUNCH(H_, LA_, C_, ...) do { \
-            static bool attr = false; \
-            if (!attr) { if (hipFuncSetAttribute((const void*)wgrad9p_kernel<H_, LA_, C_, ##__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, W9_LDS) != hipSuccess) return OCR_ERR_EXEC; attr = true; } \
+            if (ocr_allow_lds<wgrad9p_kernel<H_, LA_, C_, ##__VA_ARGS__>>(W9_LDS) != hipSuccess) return OCR_ERR_EXEC; \
             wgrad9p_kernel<H_, LA_, C_, ##__VA_ARGS__><<<grid, 512, W9_LDS, stream>>>(g); } while (0)
         // (the continuous-read-stream schedule `runc` — barrier in the middle of a step, the next step's first fragments fetched by the
         // last taps — measured equal or slower, look-ahead 2 and 5: profiles/r03x_wgrad9p_cont.log; only `make EXPERIMENTS=1` builds it)

@@ -1,8 +1,10 @@
 """Which convolution kernel the dispatcher takes for a shape — a host-only query of libocrhip.so (ocr_conv3x3_kernel_choice: the real
 dispatch code with the launch cut off), so the policy that the round's measurements settled is pinned without a GPU: the headline net's
 ten launches (profiles/r03_final_kernel_stats.md), the variable-width and configs[4] shapes, and the refusals."""
+import importlib.util
 import os
 
+import numpy as np
 import pytest
 
 from lstm_ctc_ocr_amd import _native as nat
@@ -45,3 +47,24 @@ def test_other_workloads_and_refusals():
     assert c(64, 64, 4, 96, 128) == "gemm"                   # C_in % 64 != 0
     assert c(32, 64, 4, 256, 256, bias=False, relu=False, mask=True, accumulate=True) == "conv_k3/D"     # accumulate form exists there
     assert c(64, 64, 8, 256, 256, pool=(2, 1)) == "gemm"     # no fused pool of that window
+
+
+_spec = importlib.util.spec_from_file_location("make_conv_plan_table", os.path.join(os.path.dirname(__file__), "golden", "make_conv_plan_table.py"))
+table = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(table)
+
+
+@pytest.mark.parametrize("setting", list(table.SETTINGS))
+def test_every_query_reproduces_the_recorded_policy(setting, tmp_path):
+    """All five host-only queries over the whole shape x flag grid of tests/golden/conv_plan_table.npz, under each knob setting (one child
+    interpreter per setting): the answers the table recorded, exactly."""
+    out = str(tmp_path / "answers.npz")
+    assert table.query_in_child(setting, out, nat.LIB_PATH).wait() == 0
+    with np.load(os.path.join(os.path.dirname(table.__file__), "conv_plan_table.npz")) as want, np.load(out) as got:
+        S = want["shapes"]
+        assert np.array_equal(S, table.shapes()), "the grid changed: regenerate the table from the library it was recorded with"
+        for k in ("choice", "accum", "pool", "stats", "bnbwd"):
+            w, g = want[setting + "/" + k], got[k]
+            bad = np.argwhere(w != g)
+            assert not len(bad), "%s %s: %d answers differ, first (Nb, W, H, Cin, Cout) = %s index %s: recorded %s, now %s" % (
+                setting, k, len(bad), S[bad[0][0]].tolist(), bad[0].tolist(), w[tuple(bad[0])], g[tuple(bad[0])])

@@ -1,6 +1,6 @@
 """Shader clock the halo convolution kernel really runs at: workgroup 0 stamps the shader-clock counter (s_memtime) and the 100 MHz
 wall clock (s_memrealtime) at entry and exit (ocr_conv_halo_clock_debug); MHz = d(shader) / d(wall) * 100.
-    python tools/clock_probe.py            (GPU box; OCR_HALO_ABL=5 in the environment = MFMA-only ablation of the same kernel)"""
+    python tools/clock_probe.py            (GPU box)"""
 import os
 import sys
 
@@ -24,6 +24,6 @@ for name, W, H, Ci, Co in (("conv2", 128, 16, 64, 128), ("conv3_2", 64, 8, 256, 
             torch.cuda.synchronize()
             d = dbg.cpu().numpy()
             mhz.append((d[2] - d[0]) / max(1, d[3] - d[1]) * 100.0); us.append((d[3] - d[1]) / 100.0)
-    print('%-8s ABL=%s: workgroup 0 lived %.1f us, shader clock %.0f MHz (min %.0f max %.0f)' % (
-        name, os.environ.get('OCR_HALO_ABL', '0'), np.median(us), np.median(mhz), min(mhz), max(mhz)), flush=True)
+    print('%-8s workgroup 0 lived %.1f us, shader clock %.0f MHz (min %.0f max %.0f)' % (
+        name, np.median(us), np.median(mhz), min(mhz), max(mhz)), flush=True)
 nat.call("ocr_conv_halo_clock_debug", None)
