@@ -76,7 +76,8 @@ int ocr_gemm_nt_bf16(const void* P, long ldp, const void* Q, long ldq, void* out
 int ocr_set_gemm_engine(int use_large_tile);
 /* 3x3 SAME stride-1 convolution, x bf16 [Nb,W,H,Cin], wpack bf16 [Cout][3][3][Cin], y [Nb,W,H,Cout]
  * (conv_single network.py:160-191; also its data gradient with flipped/transposed weights).  The result does not depend on which kernel
- * the dispatcher takes beyond fp32 summation order (environment OCR_CONV_K2 / OCR_CONV_K3 / OCR_K2_CFG select for the parity tests). */
+ * the dispatcher takes beyond fp32 summation order (ocr_set_gemm_engine and the environment knobs OCR_CONV_K2 / OCR_CONV_K3 / OCR_K2_CFG /
+ * OCR_CONV_WS select among them for the parity tests: the whole list, and the test file that forces each, is DESIGN section 8). */
 int ocr_conv3x3_bf16(const void* x, const void* wpack, void* y, int Nb, int W, int H, int Cin, int Cout,
                      const float* bias, const void* mask, int flags, void* stream);
 /* The convolution that also leaves the batch-norm statistics of its output behind (network.py:173-178: conv -> bias -> batch_norm):
@@ -143,6 +144,15 @@ int ocr_set_wgrad_engine(int engine);
 /* dw f32 [3][3][Cin][Cout] (TF HWIO) += conv weight gradient; dbias (may be NULL) += sum over pixels of dy */
 int ocr_conv3x3_wgrad_bf16(const void* x, const void* dy, float* dw, float* dbias, int Nb, int W, int H, int Cin,
                            int Cout, int splits, void* stream);
+/* Which kernel computes that weight gradient - a host-only query like ocr_conv3x3_kernel_choice (nothing is launched, works without a
+ * GPU; the dispatchers' own decisions, which the launches read too).  has_workspace != 0: as called through ocr_conv3x3_wgrad_ws_bf16 /
+ * _defer_bf16 with a workspace of ocr_conv3x3_wgrad_workspace_size bytes; 0: ocr_conv3x3_wgrad_bf16.  Returns kernel | S << 8 with S the
+ * number of splits of the pixel contraction (slabs of the slab kernels, atomic partial sums of the others) and kernel =
+ * 0 wgrad9_kernel, 1 / 2 wgrad9p<4> / <8> (plane layout, whole-image steps), 3 / 4 their zero-row instances (general widths),
+ * 5 gemm_tn2 nine-tap, 6 gemm_tn2 paired-tap (Cin = 64), 7 / 8 gemm_tn_kernel<1, 4, 4> / <1, 2, 2> (register-staged 128 x 128 / 64 x 64
+ * tiles); a NEGATIVE value (-OCR_STATUS_INVALID) for sizes the entry points refuse.  Depends on ocr_set_wgrad_engine and on the knobs
+ * OCR_W9_PLANES / OCR_W9P_GENW. */
+int ocr_conv3x3_wgrad_kernel_choice(int Nb, int W, int H, int Cin, int Cout, int has_workspace, int splits);
 
 /* the same through a caller-owned workspace of ocr_conv3x3_wgrad_workspace_size() bytes (0: shape not covered, the call then
  * behaves like ocr_conv3x3_wgrad_bf16): all nine taps from one staged tile, per-split partial slabs summed in a fixed order by a

@@ -49,6 +49,7 @@ _SIGS = {
     "ocr_gemm_tn_split_workspace_floats": ([_I, _I, _I], _L),
     "ocr_gemm_tn_split_bf16": ([_P, _L, _P, _L, _P, _L, _I, _I, _I, _F, _P, _P, _L, _P], _I),
     "ocr_conv3x3_wgrad_bf16": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P], _I),
+    "ocr_conv3x3_wgrad_kernel_choice": ([_I, _I, _I, _I, _I, _I, _I], _I),
     "ocr_conv3x3_wgrad_workspace_size": ([_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_conv3x3_wgrad_ws_bf16": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P], _I),
     "ocr_conv3x3_wgrad_defer_bf16": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, ctypes.POINTER(_I),

@@ -80,8 +80,10 @@ __device__ __forceinline__ void dma16_saddr(unsigned lds_dst, unsigned voff, con
 
 // Tuning knobs (tile policies, stage counts, ...): read from the environment only by `make EXPERIMENTS=1` builds — the A/B tools load that
 // library through OCR_NATIVE_LIB; the product library uses the measured defaults.  Kernel-selection knobs that the parity tests force
-// (OCR_CONV_K2 / OCR_CONV_K3 / OCR_K2_CFG / OCR_CONV_WS / OCR_W9_PLANES / OCR_LSTM_PROTO / OCR_LSTM_ROWS) are read by both.  The 3x3
-// convolution's knobs, of both kinds, are all read in one place: gemm.hip's read_conv_knobs().
+// are read by both: OCR_CONV_K2 / OCR_CONV_K3 / OCR_K2_CFG / OCR_CONV_WS / OCR_LSTM_PROTO / OCR_LSTM_ROWS (tests/test_gpu_kernels.py) and
+// OCR_W9_PLANES / OCR_W9P_GENW / OCR_TN3_NST, with the engine generations OCR_GEMM_ENGINE / OCR_WGRAD_ENGINE
+// (tests/test_gpu_kernel_generations.py); DESIGN section 8 has the table.  The 3x3 convolution's knobs, of both kinds, are all read in one
+// place: gemm.hip's read_conv_knobs().
 static inline const char* ocr_tune_env(const char* name) {
 #ifdef OCR_EXPERIMENTS
     return getenv(name);

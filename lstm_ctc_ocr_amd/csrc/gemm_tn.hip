@@ -224,6 +224,9 @@ int tn2_try_dispatch(const void* A, long lda, const void* B, long ldb, float* ou
                      hipStream_t stream, int nbatch = 1, long sA = 0, long sB = 0, long sO = 0, long sC = 0);
 int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, int Nb, int W, int H, int Cin, int Cout,
                         void* workspace, size_t ws_bytes, hipStream_t stream, void* defer_job = nullptr, int* defer_blocks = nullptr);
+// the two generations' decisions with the launch cut off (what their dispatchers launch by): kernel code and split count, -1 = not covered
+int tn2_choice(int Mk, int I, int J, int mode, int splits, int nbatch, int* S);
+int wgrad9_choice(int Nb, int W, int H, int Cin, int Cout, int* S);
 static int g_use_tn2 = 1, g_use_w9 = 1;
 // 2 (default): nine-tap slab kernel (wgrad9.hip) where a workspace is given and the shape is covered, else as 1;
 // 1: LDS-DMA per-tap tiles with fp32 atomics (gemm_tn2.hip); 0: register-staged kernel (this file)
@@ -350,6 +353,14 @@ extern "C" int ocr_conv3x3_wgrad_defer_bf16(const void* x, const void* dy, float
     return ocr_conv3x3_wgrad_bf16(x, dy, dw, dbias, Nb, W, H, Cin, Cout, 0, stream);
 }
 
+// register-staged 3x3 weight gradient: 128 x 128 tiles (gemm_tn_kernel<1, 4, 4>) from 128 channels on both sides, else 64 x 64 (<1, 2, 2>)
+static void tn_wgrad_plan(int Mk, int Cin, int Cout, int splits, bool* big, int* k_per_split) {
+    *big = (Cin >= 128 && Cout >= 128);
+    long tiles = 9L * (*big ? (long)ceil_div(Cin, 128) * ceil_div(Cout, 128) : (long)ceil_div(Cin, 64) * ceil_div(Cout, 64));
+    if (splits <= 0) splits = pick_splits(tiles, Mk);
+    *k_per_split = ceil_div(ceil_div(Mk, splits), 32) * 32;
+}
+
 // dW[3][3][Cin][Cout] (fp32, TF layout) += sum over pixels of x[shifted pixel][ci] * dy[pixel][co]
 extern "C" int ocr_conv3x3_wgrad_bf16(const void* x, const void* dy, float* dw, float* dbias, int Nb, int W, int H,
                                       int Cin, int Cout, int splits, void* stream) {
@@ -363,9 +374,21 @@ extern "C" int ocr_conv3x3_wgrad_bf16(const void* x, const void* dy, float* dw, 
     g.A = (const bf16_t*)x; g.B = (const bf16_t*)dy; g.lda = Cin; g.ldb = Cout;
     g.Mk = Nb * W * H; g.I = Cin; g.J = Cout; g.cW = W; g.cH = H; g.cC = Cin;
     g.out = dw; g.ldo = Cout; g.scale = 1.0f; g.colsum = dbias;
-    bool big = (Cin >= 128 && Cout >= 128);
-    long tiles = 9L * (big ? (long)ceil_div(Cin, 128) * ceil_div(Cout, 128) : (long)ceil_div(Cin, 64) * ceil_div(Cout, 64));
-    if (splits <= 0) splits = pick_splits(tiles, g.Mk);
-    g.k_per_split = ceil_div(ceil_div(g.Mk, splits), 32) * 32;
+    bool big;
+    tn_wgrad_plan(g.Mk, Cin, Cout, splits, &big, &g.k_per_split);
     return big ? launch_tn<1, 4, 4>(g, 9, (hipStream_t)stream) : launch_tn<1, 2, 2>(g, 9, (hipStream_t)stream);
+}
+
+// Which kernel ocr_conv3x3_wgrad_ws_bf16 / _defer_bf16 (has_workspace != 0: a workspace of ocr_conv3x3_wgrad_workspace_size bytes) or
+// ocr_conv3x3_wgrad_bf16 (has_workspace = 0) runs for a shape under the current engine and knobs: the same three decisions in the same
+// order as those entry points, nothing launched.  kernel code (ocr_hip.h) | split count << 8, or -OCR_ERR_INVALID.
+extern "C" int ocr_conv3x3_wgrad_kernel_choice(int Nb, int W, int H, int Cin, int Cout, int has_workspace, int splits) {
+    if (Nb <= 0 || W <= 0 || H <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 7) || (Cout & 7)) return -OCR_ERR_INVALID;
+    int S = 0, k;
+    if (g_use_w9 && has_workspace && splits <= 0 && (k = wgrad9_choice(Nb, W, H, Cin, Cout, &S)) >= 0) return k | (S << 8);
+    const int Mk = Nb * W * H;
+    if (g_use_tn2 && (k = tn2_choice(Mk, Cin, Cout, 1, splits, 1, &S)) >= 0) return (k == 2 ? 6 : 5) | (S << 8);
+    bool big; int kps;
+    tn_wgrad_plan(Mk, Cin, Cout, splits, &big, &kps);
+    return (big ? 7 : 8) | (ceil_div(Mk, kps) << 8);
 }

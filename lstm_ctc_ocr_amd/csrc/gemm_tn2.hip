@@ -272,20 +272,15 @@ __global__ __launch_bounds__(64 * NWV) void gemm_tn2_kernel(Tn2Args g) {
         }
 }
 
-// returns -1 if the shape is not covered
-int tn2_try_dispatch(const void* A, long lda, const void* B, long ldb, float* out, long ldo, int Mk, int I, int J, int mode,
-                     int grp, int skip, long a_row_off, int cW, int cH, int cC, float scale, int splits, float* colsum,
-                     hipStream_t stream, int nbatch = 1, long sA = 0, long sB = 0, long sO = 0, long sC = 0) {
+// Coverage, partition and split count: what tn2_try_dispatch launches by and ocr_conv3x3_wgrad_kernel_choice reports (tn2_choice).
+// false: the shape is not covered (the caller falls back to gemm_tn.hip).
+struct Tn2Plan { bool pair, wide; int taps, IT, JT, XS, XJ, XI, S; long tiles; };
+static bool tn2_plan(int Mk, int I, int J, int mode, int splits, int nbatch, Tn2Plan* p) {
     const bool pair = (mode == 1 && I == 64);          // Cin == 64: two taps per A tile
-    if ((!pair && (I & 127)) || (J & 127) || Mk < 256) return -1;
-    Tn2Args g = {};
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.lda = lda; g.ldb = ldb; g.Mk = Mk; g.I = I; g.J = J;
-    g.grp = grp; g.skip = skip; g.a_row_off = a_row_off; g.cW = cW; g.cH = cH; g.cC = cC;
-    g.out = out; g.ldo = ldo; g.scale = scale; g.colsum = colsum;
+    if ((!pair && (I & 127)) || (J & 127) || Mk < 256) return false;
     const int taps = pair ? 5 : (mode == 1 ? 9 : 1);
     const int IT = pair ? 1 : I / 128, JT = J / 128;
     const long tiles = (long)taps * IT * JT * nbatch;
-    g.nbatch = nbatch; g.sA = sA; g.sB = sB; g.sO = sO; g.sC = sC;
     int maxs = Mk / 768; if (maxs < 1) maxs = 1;      // at least 12 K steps per workgroup: shorter runs are all prologue + atomics
                                                       // (Mk = 4032: 4-6 splits measured best, tools/tn_plain_probe.py)
     // Workgroup count and XCD partition (sweep: tools/wgrad_part_sweep.py).  The K loop is latency-bound (two LDS stages, one
@@ -326,9 +321,34 @@ int tn2_try_dispatch(const void* A, long lda, const void* B, long ldb, float* ou
             bXS = xs; bXJ = xj; bXI = xi; bS = sp; best = 0;
         }
     }
-    if (best == 1e300) return -1;
-    splits = bS;
-    g.XS = bXS; g.XJ = bXJ; g.XI = bXI; g.taps = taps; g.itl = IT / bXI; g.jtl = JT / bXJ;
+    if (best == 1e300) return false;
+    p->pair = pair; p->wide = wide; p->taps = taps; p->IT = IT; p->JT = JT; p->tiles = tiles;
+    p->XS = bXS; p->XJ = bXJ; p->XI = bXI; p->S = bS;
+    return true;
+}
+// 0 = plain product, 1 = nine-tap, 2 = paired-tap (the MODE of gemm_tn2_kernel), *S = its split count; -1 = not covered
+int tn2_choice(int Mk, int I, int J, int mode, int splits, int nbatch, int* S) {
+    Tn2Plan p;
+    if (!tn2_plan(Mk, I, J, mode, splits, nbatch, &p)) return -1;
+    *S = p.S;
+    return p.pair ? 2 : mode;
+}
+
+// returns -1 if the shape is not covered
+int tn2_try_dispatch(const void* A, long lda, const void* B, long ldb, float* out, long ldo, int Mk, int I, int J, int mode,
+                     int grp, int skip, long a_row_off, int cW, int cH, int cC, float scale, int splits, float* colsum,
+                     hipStream_t stream, int nbatch = 1, long sA = 0, long sB = 0, long sO = 0, long sC = 0) {
+    Tn2Plan p;
+    if (!tn2_plan(Mk, I, J, mode, splits, nbatch, &p)) return -1;
+    const bool pair = p.pair, wide = p.wide;
+    const long tiles = p.tiles;
+    Tn2Args g = {};
+    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.lda = lda; g.ldb = ldb; g.Mk = Mk; g.I = I; g.J = J;
+    g.grp = grp; g.skip = skip; g.a_row_off = a_row_off; g.cW = cW; g.cH = cH; g.cC = cC;
+    g.out = out; g.ldo = ldo; g.scale = scale; g.colsum = colsum;
+    g.nbatch = nbatch; g.sA = sA; g.sB = sB; g.sO = sO; g.sC = sC;
+    splits = p.S;
+    g.XS = p.XS; g.XJ = p.XJ; g.XI = p.XI; g.taps = p.taps; g.itl = p.IT / p.XI; g.jtl = p.JT / p.XJ;
     g.k_per_split = ceil_div(ceil_div(Mk, splits), 64) * 64;
     g.owned = (mode == 0 && splits == 1) ? 1 : 0;
     static int cfg = -1;                           // A/B knob OCR_TN2_PIPE: 0 = 64-row stages x 2 (default), 1 = 32 x 4, 2 = 32 x 3, 3 = 64 x 3

@@ -1161,14 +1161,44 @@ extern "C" int ocr_conv3x3_wgrad_workspace_size(int Nb, int W, int H, int Cin, i
     return OCR_OK;
 }
 
+// Which slab kernel takes a covered shape: the decision wgrad9_try_dispatch launches by and ocr_conv3x3_wgrad_kernel_choice reports
+// (gemm_tn.hip; the W9K_* codes are the first five of that query's).  -1: w9_plan refuses the shape.  *variant_out = which wgrad9_kernel
+// instance W9K_WGRAD9 stands for: the experiments build's OCR_W9_VARIANT, 0 (the measured default) in the product library and at H = 2.
+enum { W9K_WGRAD9 = 0, W9K_P4 = 1, W9K_P8 = 2, W9K_P4_ZERO_ROW = 3, W9K_P8_ZERO_ROW = 4 };
+static int w9_choose(int M, int W, int H, int Cin, int Cout, W9Plan* p, int* variant_out = nullptr) {
+    if (!w9_plan(M, W, H, Cin, Cout, p)) return -1;
+    static int variant = -1;                    // A/B knob OCR_W9_VARIANT (see the table below); default 0
+    if (variant < 0) { const char* e = ocr_tune_env("OCR_W9_VARIANT"); variant = e ? atoi(e) : 0; }
+    if (variant_out) *variant_out = H == 2 ? 0 : variant;   // H = 2 (a 4-row read block spans two image columns): only the redirecting default handles it
+    // plane-layout kernel where it covers the shape (A/B knob OCR_W9_PLANES = 0: wgrad9_kernel everywhere)
+    static int planes = -1;
+    if (planes < 0) { const char* e = getenv("OCR_W9_PLANES"); planes = e ? atoi(e) : 1; }
+    // whole-image steps (W % NC == 0) or, round 6, any W >= NC through the zero-row instances (GENW)
+    static int genw = -1;                       // A/B knob OCR_W9P_GENW = 0: general widths stay on wgrad9_kernel; 2: the zero-row instances on whole-image shapes too (tests, timing)
+    if (genw < 0) { const char* e = getenv("OCR_W9P_GENW"); genw = e ? atoi(e) : 1; }
+    const bool whole = (H == 4 || H == 8) && W % (128 / H) == 0;
+    const bool use_p = planes && variant == 0 && (H == 4 || H == 8) && (whole || (genw && W >= 128 / H)) && M % 128 == 0 &&
+                       (long)M * (Cin > Cout ? Cin : Cout) * 2 < 0x7fffffffL;
+    if (!use_p) return W9K_WGRAD9;              // (H = 2 and H = 16 always: wgrad9p has no instance for them)
+    if (!whole || (genw == 2 && W >= 128 / H)) return H == 4 ? W9K_P4_ZERO_ROW : W9K_P8_ZERO_ROW;
+    return H == 4 ? W9K_P4 : W9K_P8;
+}
+int wgrad9_choice(int Nb, int W, int H, int Cin, int Cout, int* S) {
+    W9Plan p;
+    const int k = w9_choose(Nb * W * H, W, H, Cin, Cout, &p);
+    if (k >= 0) *S = p.S;
+    return k;
+}
+
 // -1: shape not covered or workspace too small (caller falls back to the atomics kernels)
 int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, int Nb, int W, int H, int Cin, int Cout,
                         void* workspace, size_t ws_bytes, hipStream_t stream, void* defer_job, int* defer_blocks) {
     W9Plan p;
     const int M = Nb * W * H;
-    if (!workspace || !w9_plan(M, W, H, Cin, Cout, &p) || ws_bytes < p.bytes) return -1;
-    static int variant = -1;                    // A/B knob OCR_W9_VARIANT (see the table below); default 0
-    if (variant < 0) { const char* e = ocr_tune_env("OCR_W9_VARIANT"); variant = e ? atoi(e) : 0; }
+    int variant = 0;
+    if (!workspace) return -1;
+    const int kern = w9_choose(M, W, H, Cin, Cout, &p, &variant);
+    if (kern < 0 || ws_bytes < p.bytes) return -1;
     W9Args g = {};
     g.X = (const bf16_t*)x; g.dY = (const bf16_t*)dy; g.M = M; g.Cin = Cin; g.Cout = Cout; g.cW = W; g.cH = H;
     g.k_per_split = p.k_per_split; g.S = p.S; g.T_ci = p.T_ci; g.T_co = p.T_co; g.map = p.map;
@@ -1181,15 +1211,7 @@ int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, 
 #define W9C_LAUNCH(LA_, NS_, NB_, DBG_) do { \
         if (ocr_allow_lds<wgrad9c_kernel<LA_, NS_, NB_, DBG_>>(W9_LDS) != hipSuccess) return OCR_ERR_EXEC; \
         wgrad9c_kernel<LA_, NS_, NB_, DBG_><<<grid, 512, W9_LDS, stream>>>(g); } while (0)
-    // plane-layout kernel where it covers the shape (A/B knob OCR_W9_PLANES = 0: wgrad9_kernel everywhere)
-    static int planes = -1;
-    if (planes < 0) { const char* e = getenv("OCR_W9_PLANES"); planes = e ? atoi(e) : 1; }
-    // whole-image steps (W % NC == 0) or, round 6, any W >= NC through the zero-row instances (GENW)
-    static int genw = -1;                       // A/B knob OCR_W9P_GENW = 0: general widths stay on wgrad9_kernel; 2: the zero-row instances on whole-image shapes too (tests, timing)
-    if (genw < 0) { const char* e = getenv("OCR_W9P_GENW"); genw = e ? atoi(e) : 1; }
-    const bool whole = (H == 4 || H == 8) && W % (128 / H) == 0;
-    const bool use_p = planes && variant == 0 && (H == 4 || H == 8) && (whole || (genw && W >= 128 / H)) && M % 128 == 0 &&
-                       (long)M * (Cin > Cout ? Cin : Cout) * 2 < 0x7fffffffL;
+    const bool use_p = kern != W9K_WGRAD9;
     if (use_p) {
         // (look-ahead 3 and 4 of the fragment read stream measured equal to 2: profiles/r03s_wgrad9p.log)
 #define W9P_LAUNCH(H_, LA_, C_, ...) do { \
@@ -1205,11 +1227,12 @@ int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, 
             else { if (cont == 1) W9P_LAUNCH(8, 2, true); else W9P_LAUNCH(8, 5, true); }
         } else
 #endif
-        if (!whole || (genw == 2 && W >= 128 / H)) { if (H == 4) W9P_LAUNCH(4, 2, false, true); else W9P_LAUNCH(8, 2, false, true); }
-        else if (H == 4) W9P_LAUNCH(4, 2, false); else W9P_LAUNCH(8, 2, false);
+        if (kern == W9K_P4_ZERO_ROW) W9P_LAUNCH(4, 2, false, true);
+        else if (kern == W9K_P8_ZERO_ROW) W9P_LAUNCH(8, 2, false, true);
+        else if (kern == W9K_P4) W9P_LAUNCH(4, 2, false); else W9P_LAUNCH(8, 2, false);
 #undef W9P_LAUNCH
     } else
-    switch (H == 2 ? 0 : variant) {             // H = 2 (a 4-row read block spans two image columns): only the redirecting default handles it
+    switch (variant) {
 #ifdef OCR_EXPERIMENTS      // timing variants / ablations of tools/w9_variants.py (round 2, all measured slower or equal)
         case 1: W9_LAUNCH(3, 0, false); break;
         case 2: W9_LAUNCH(4, 0, false); break;

@@ -229,6 +229,20 @@ def conv3x3_wgrad_workspace_bytes(Nb, W, H, Cin, Cout):
     return sz.value
 
 
+WGRAD_KERNEL_NAMES = ("wgrad9", "wgrad9p<4>", "wgrad9p<8>", "wgrad9p<4>/zero-row", "wgrad9p<8>/zero-row", "gemm_tn2/nine-tap",
+                      "gemm_tn2/paired-tap", "gemm_tn<1,4,4>", "gemm_tn<1,2,2>")
+
+
+def conv3x3_wgrad_kernel_choice(Nb, W, H, Cin, Cout, *, workspace=True, splits=0):
+    """(kernel name, split count S) of the 3x3 weight gradient for this shape (host-only query, no GPU needed): what conv3x3_wgrad /
+    conv3x3_wgrad_deferred run with a workspace of conv3x3_wgrad_workspace_bytes (workspace=True) or without one, under the current
+    wgrad engine and knobs.  S = slabs of the slab kernels, splits of the pixel contraction (atomics) of the others."""
+    rc = nat.lib().ocr_conv3x3_wgrad_kernel_choice(int(Nb), int(W), int(H), int(Cin), int(Cout), int(bool(workspace)), int(splits))
+    if rc < 0:
+        raise nat.NativeError("ocr_conv3x3_wgrad_kernel_choice failed: status %d (%s)" % (-rc, nat.status_string(-rc)))
+    return WGRAD_KERNEL_NAMES[rc & 255], rc >> 8
+
+
 def conv3x3_wgrad(x, dy, dw, splits=0, dbias=None, workspace=None):
     """dw [3,3,Cin,Cout] f32 += weight gradient; dbias += column sums of dy.  With `workspace` (uint8 tensor of at least
     conv3x3_wgrad_workspace_bytes) the nine-tap slab kernel runs where it applies."""

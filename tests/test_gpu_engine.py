@@ -97,18 +97,18 @@ GRAD_L2_BAR = {'default': 4e-2, 'conv4_1/weights': 2e-2, 'conv4_1/conv4_1/beta':
 GRAD_L2_BAR_FP32 = 0.2       # distance to the pure-fp32 oracle (dominated by the forward rounding): measured <= 9.9e-2
 
 
-def test_train_step_parity(engine):
-    N, W = 8, 88
-    x, labels, ll, sl = make_batch(N, W, 2, 4, 2)
-    params = {k: torch.from_numpy(v) for k, v in engine.state_arrays().items()}
-    g_sim, ctc_ref = _oracle_grads(params, x, labels, ll, sl, 1e-5, sim=True)
-    g_sim_nr, _ = _oracle_grads(params, x, labels, ll, sl, 1e-5, sim=True, grad_rounding=False)
-    g_f32, ctc_f32 = _oracle_grads(params, x, labels, ll, sl, 1e-5, sim=False)
-    # run forward+backward only (no optimiser) and compare raw gradients
-    sp = engine.plan(N, W)
-    engine._bind(sp, x, sl, labels, ll)
-    engine._run(sp, 'fb')
-    torch.cuda.synchronize()
+def oracle_step(params, x, labels, ll, sl, wd=1e-5):
+    """The oracle's gradients and CTC losses for one batch: bf16-simulating (with / without gradient rounding) and pure fp32."""
+    g_sim, ctc_ref = _oracle_grads(params, x, labels, ll, sl, wd, sim=True)
+    g_sim_nr, _ = _oracle_grads(params, x, labels, ll, sl, wd, sim=True, grad_rounding=False)
+    g_f32, ctc_f32 = _oracle_grads(params, x, labels, ll, sl, wd, sim=False)
+    return g_sim, g_sim_nr, g_f32, ctc_ref, ctc_f32
+
+
+def check_step_against_oracle(engine, sp, oracle):
+    """Loss and raw gradients of the forward + backward pass that just ran on plan `sp` against oracle_step()'s answer, by the bars above
+    (shared with test_gpu_kernel_generations.py, which runs the same step under the other engine generations)."""
+    g_sim, g_sim_nr, g_f32, ctc_ref, ctc_f32 = oracle
     ctc_dev = float(sp.costs.cpu().numpy().mean())
     assert abs(ctc_dev - ctc_ref) / ctc_ref < 1e-3, (ctc_dev, ctc_ref)
     assert abs(ctc_dev - ctc_f32) / ctc_f32 < 1e-3, (ctc_dev, ctc_f32)          # north-star bar against the fp32 graph
@@ -133,6 +133,19 @@ def test_train_step_parity(engine):
         if not (e_sim < GRAD_L2_BAR.get(name, GRAD_L2_BAR['default']) and e_f32 < GRAD_L2_BAR_FP32):
             bad.append((name, e_sim, e_f32))
     assert not bad, bad
+
+
+def test_train_step_parity(engine):
+    N, W = 8, 88
+    x, labels, ll, sl = make_batch(N, W, 2, 4, 2)
+    params = {k: torch.from_numpy(v) for k, v in engine.state_arrays().items()}
+    oracle = oracle_step(params, x, labels, ll, sl)
+    # run forward+backward only (no optimiser) and compare raw gradients
+    sp = engine.plan(N, W)
+    engine._bind(sp, x, sl, labels, ll)
+    engine._run(sp, 'fb')
+    torch.cuda.synchronize()
+    check_step_against_oracle(engine, sp, oracle)
 
 
 @pytest.mark.parametrize("N,W", [(8, 88), (64, 256)])

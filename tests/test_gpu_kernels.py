@@ -6,6 +6,7 @@ relative) when the output is stored as bf16; CTC loss 1e-4 relative (north star 
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -18,6 +19,9 @@ from lstm_ctc_ocr_amd import ops
 from oracle import ctc as octc
 from oracle import decode as odec
 from oracle import graph as og
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from conv_shapes import CONV_SHAPES  # noqa: E402
 
 BF = torch.bfloat16
 
@@ -296,24 +300,7 @@ def _conv_ref(x, w, b):   # x [N,W,H,C], w HWIO
     return y + b
 
 
-@pytest.mark.parametrize("Nb,W,H,Ci,Co", [(4, 16, 8, 64, 128), (2, 12, 4, 256, 512), (64, 64, 4, 256, 512), (3, 20, 16, 64, 128),
-                                          (16, 32, 16, 64, 128), (64, 128, 8, 64, 256), (5, 52, 4, 128, 192), (32, 64, 4, 512, 512),
-                                          (7, 22, 8, 128, 256), (32, 64, 2, 512, 512), (3, 18, 2, 64, 128), (9, 64, 2, 128, 64),
-                                          (17, 62, 4, 128, 128), (9, 30, 16, 64, 256),       # ragged last tiles of the 256- / 128-pixel kernels
-                                          (4, 128, 8, 128, 128), (6, 192, 4, 192, 64),       # plane-layout kernel: several tiles per image, 3 chunks
-                                          (8, 48, 16, 128, 64), (16, 32, 16, 128, 128), (8, 64, 16, 64, 64),    # ... at H = 16 (one / two halo buffers)
-                                          (32, 40, 4, 128, 128), (32, 24, 8, 64, 128), (16, 50, 8, 128, 64),    # ... tiles crossing image boundaries (general width)
-                                          # weight-stationary persistent kernel (conv_ws, round 5): small grids (fewer tiles than workgroups, three channel
-                                          # tiles = no XCD map, several images per workgroup run); taken by default only from two tiles per CU, forced with OCR_CONV_WS=2
-                                          (2, 32, 16, 64, 128), (3, 24, 16, 128, 192), (5, 48, 8, 128, 64), (40, 64, 16, 64, 64),
-                                          # the EXACT shapes of the benchmarked step (BASELINE configs[1], N = 64, W = 256): conv2, conv3_1, conv3_2, conv4_2
-                                          # (conv4_1 is (64, 64, 4, 256, 512) above) — the dispatcher's full-chip tiles / 64-split slabs only exist at this size
-                                          (64, 128, 16, 64, 128), (64, 64, 8, 128, 256), (64, 64, 8, 256, 256), (64, 64, 4, 512, 512),
-                                          # ... and the extremes of configs[3] (W = 80 and W = 320 padded batches)
-                                          (64, 40, 16, 64, 128), (64, 20, 4, 512, 512), (64, 80, 8, 256, 256), (64, 80, 4, 256, 512),
-                                          # ... and widths that are no multiple of the weight-gradient kernel's step (round 6: wgrad9p's zero-row instances — every
-                                          # step of (32, 33, 4) / (16, 17, 8) crosses an image boundary at another column; W = 79 = a 316-pixel configs[3] batch)
-                                          (32, 33, 4, 64, 64), (16, 17, 8, 64, 64), (64, 79, 4, 256, 512), (64, 79, 8, 256, 256), (32, 47, 4, 128, 64)])
+@pytest.mark.parametrize("Nb,W,H,Ci,Co", CONV_SHAPES)      # tests/conv_shapes.py: shared with the engine-generation and dispatch-policy tests
 def test_conv3x3_fwd_dgrad_wgrad(dev, Nb, W, H, Ci, Co):
     x = bf(gen((Nb, W, H, Ci), 1)); w = bf(gen((3, 3, Ci, Co), 2, 0.05)); b = gen((Co,), 3)
     ref = _conv_ref(x, w, b)
