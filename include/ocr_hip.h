@@ -365,7 +365,8 @@ int ocr_guard_flag(const void* guard_addrs, int nguard, float* flag_out, void* s
 int ocr_captcha_synth(const int* params, int n_images, int words_per_image, int max_glyphs, const void* atlas, const int* stamp, int n_stamp,
                       void* out, int W, int out_h, int canvas_cap, int width_cap, void* stream);
 
-/* diagnostics: s_memtime stamps of workgroup 0 (NULL = off); device int64 [8 waves][64 steps][8] / [8][80][8] */
+/* diagnostics (experiments library; the product library stores the pointer and never reads it): wall-clock phase stamps of every wgrad9p_kernel
+ * workgroup, device int64 [workgroups][8] (NULL = off); tools/w9p_phases.py */
 int ocr_wgrad9_debug(void* dbg);
 
 /* ---- device probes used by the test-suite (not part of the hot path) ------------------------------------------ */

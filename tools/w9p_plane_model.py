@@ -77,7 +77,7 @@ def b_fragment_rows(g, kh, kk, lane):
     return [base + 4 * g4 + e for e in range(4)] + [base + 16 + 4 * g4 + e for e in range(4)]
 
 
-# ---- general widths (round 6, wgrad9p_kernel<H, LA, CONT, GENW = true>): a step's NC columns may cross ONE image boundary (W >= NC) ---------------------
+# ---- general widths (round 6, wgrad9p_kernel<H, GENW = true>): a step's NC columns may cross ONE image boundary (W >= NC) ---------------------
 # The planes are staged as for whole-image steps (dma_fill above works for any W: plane row 1 + c = local column c).  Where local column b of the step
 # is the first column of the next image, two contraction elements change: the +1 tap of column b - 1 and the -1 tap of column b read a ZERO ROW of the
 # plane (rows NC + 2 .. PS - 1 arrive as zeros with every stage) — the lane that supplies that pixel is redirected for that tap.

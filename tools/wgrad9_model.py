@@ -1,6 +1,8 @@
 """Host-side index model of csrc/wgrad9.hip (no GPU needed): replays the kernel's address arithmetic — LDS-DMA source
-swizzle, ds_read_b64_tr_b16 gather, tap shifts, SAME-padding masks, k permutation, accumulator ownership, split / tile map —
+swizzle, ds_read_b64_tr_b16 gather, tap shifts, SAME padding, k permutation, accumulator ownership, split / tile map —
 in numpy on small shapes and compares with a direct evaluation of  dW[t][ci][co] = sum_m X[m + shift(t)][ci] * dY[m][co].
+(Padding: the model zeroes the padded elements of the gathered fragment; the kernel gets the same zeros by pointing the lane
+that supplies such an element at a zero block, so that nothing touches the fragment between the read and the MFMA.)
 A mistake in any of the formulas shows up here before a GPU minute is spent.   python tools/wgrad9_model.py
 """
 import itertools
