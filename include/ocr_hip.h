@@ -105,6 +105,12 @@ int ocr_conv_ws_debug(void* dbg);
  * [Nb, W/kw, H/kh, Cout]; (kw, kh) = (1, 2) (feature axis) or (2, 2).  ocr_conv3x3_pool_supported() != 0 tells whether the shape is
  * covered; otherwise run ocr_conv3x3_bf16 + ocr_maxpool_fwd (ocr_conv3x3_relu_pool_bf16 then returns 2). */
 int ocr_conv3x3_pool_supported(int Nb, int W, int H, int Cin, int Cout, int kw, int kh);
+/* The training form: the same launch also writes the pool's routing codes (uint32 [Nb * W/kw * H/kh][Cout / 8], the format of
+ * ocr_maxpool_bwd_codes) and, when y is NULL, no full-resolution tensor.  Only where ocr_conv3x3_pool_codes_supported() != 0 (the kernel planned
+ * for the shape is conv_ws or an aligned-width conv_k3); elsewhere keep y and use ocr_conv3x3_relu_pool_bf16 + ocr_maxpool_bwd. */
+int ocr_conv3x3_pool_codes_supported(int Nb, int W, int H, int Cin, int Cout, int kw, int kh);
+int ocr_conv3x3_relu_pool_codes_bf16(const void* x, const void* wpack, void* y, void* pooled, void* codes, int Nb, int W, int H, int Cin,
+                                     int Cout, const float* bias, int kw, int kh, void* stream);
 int ocr_conv3x3_relu_pool_bf16(const void* x, const void* wpack, void* y, void* pooled, int Nb, int W, int H, int Cin, int Cout,
                                const float* bias, int kw, int kh, void* stream);
 /* out[I][ldo] (f32) += scale * A^T B, A bf16 [Mk][lda], B bf16 [Mk][ldb]  (weight gradients of matmul layers);
@@ -200,6 +206,12 @@ int ocr_conv1_pool_bwd(const float* x, const float* w, const float* bias, const 
 int ocr_maxpool_fwd(const void* x, void* y, int Nb, int W, int H, int C, int kw, int kh, void* stream);
 int ocr_maxpool_bwd(const void* x, const void* dy, void* dx, int Nb, int W, int H, int C, int kw, int kh,
                     int relu_mask, void* stream);
+/* ocr_maxpool_bwd from the pool's routing codes instead of its full-resolution input x: codes = uint32 [Nb * W/kw * H/kh][C / 8], one word per
+ * (window, 8-channel group), 4 bits per channel - bits 0-1 the index of the window's first maximum in TF scan order (a * kh + b, a over W),
+ * bit 2 maximum > 0 - as a forward pass that compares the bf16-rounded values writes them.  (kw, kh) = (2, 2) or (1, 2); dx is
+ * bit-identical to ocr_maxpool_bwd's. */
+int ocr_maxpool_bwd_codes(const void* codes, const void* dy, void* dx, int Nb, int W, int H, int C, int kw, int kh,
+                          int relu_mask, void* stream);
 /* training-mode batch norm over rows of x[M][C] (network.py:176-178): batch statistics, biased variance.  `workspace` is
  * ocr_bn_workspace_bytes(M, C) bytes of caller-owned scratch (per-block partial sums; neither zeroed nor kept) */
 size_t ocr_bn_workspace_bytes(long M, int C);
@@ -220,6 +232,13 @@ int ocr_bn_train_fwd2(const void* x, void* y, const float* gamma, const float* b
 int ocr_bn_train_bwd2(const void* x, const void* y, const void* dy, void* dx, const float* gamma, const float* save_mean,
                       const float* save_rstd, float* dgamma, float* dbeta, long M, int C, int relu, void* workspace, int pooled_dy,
                       int partial_rows, void* stream);
+/* The training forms where that pool is the layer's ONLY consumer: the apply pass writes pooled and the pool's routing codes (uint32 [M / 2][C / 8],
+ * the format of ocr_maxpool_bwd_codes for the 1 x 2 window) and no y; the backward passes take the winner of each pair and its ReLU mask from
+ * the codes.  dx, dgamma and dbeta are bit-identical to ocr_bn_train_bwd2(pooled_dy = 1) on the y of ocr_bn_train_fwd2. */
+int ocr_bn_train_fwd_codes(const void* x, const float* gamma, const float* beta, float* save_mean, float* save_rstd, long M, int C,
+                           float eps, int relu, void* workspace, int partial_rows, void* pooled, void* codes, void* stream);
+int ocr_bn_train_bwd_codes(const void* x, const void* codes, const void* dy, void* dx, const float* gamma, const float* save_mean,
+                           const float* save_rstd, float* dgamma, float* dbeta, long M, int C, int relu, void* workspace, void* stream);
 /* partial_rows > 0 (not with pooled_dy): dy is ALREADY ReLU-masked and the workspace holds that many rows [rows][2][C] of (sum dz, sum dz *
  * xhat) from the data-gradient kernel that wrote dy — ocr_conv3x3_dgrad_bnbwd_bf16: dx = (mask_y > 0) ? conv3x3(dy, wdgrad) : 0 plus those
  * per-256-pixel-tile sums with xhat = (z - mean) * rstd, rows = ocr_conv3x3_bnbwd_rows(...) (0: shape not covered, use the separate passes).

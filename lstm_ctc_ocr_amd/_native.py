@@ -45,6 +45,8 @@ _SIGS = {
     "ocr_conv3x3_kernel_choice": ([_I, _I, _I, _I, _I, _I, _I, _I], _I),
     "ocr_conv3x3_pool_supported": ([_I, _I, _I, _I, _I, _I, _I], _I),
     "ocr_conv3x3_relu_pool_bf16": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P], _I),
+    "ocr_conv3x3_pool_codes_supported": ([_I, _I, _I, _I, _I, _I, _I], _I),
+    "ocr_conv3x3_relu_pool_codes_bf16": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P], _I),
     "ocr_gemm_tn_bf16": ([_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _L, _F, _I, _P, _P], _I),
     "ocr_gemm_tn_split_workspace_floats": ([_I, _I, _I], _L),
     "ocr_gemm_tn_split_bf16": ([_P, _L, _P, _L, _P, _L, _I, _I, _I, _F, _P, _P, _L, _P], _I),
@@ -71,6 +73,9 @@ _SIGS = {
     "ocr_bn_train_bwd": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P], _I),
     "ocr_bn_train_fwd2": ([_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P, _P, _I, _P, _P], _I),
     "ocr_bn_train_bwd2": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _I, _I, _P], _I),
+    "ocr_maxpool_bwd_codes": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P], _I),
+    "ocr_bn_train_fwd_codes": ([_P, _P, _P, _P, _P, _L, _I, _F, _I, _P, _I, _P, _P, _P], _I),
+    "ocr_bn_train_bwd_codes": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P], _I),
     "ocr_conv3x3_bnbwd_rows": ([_I, _I, _I, _I, _I], _I),
     "ocr_conv3x3_dgrad_bnbwd_bf16": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "ocr_conv3x3_stats_rows": ([_I, _I, _I, _I, _I, _I], _I),

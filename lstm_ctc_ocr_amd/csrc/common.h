@@ -47,6 +47,28 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
 __device__ __forceinline__ float bf_lo(uint32_t p) { return __uint_as_float(p << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
 
+// The routing codes of a max-pool window for one 8-channel group, 4 bits per channel (conv1_pool_code's format, nn_ops.hip): index of the FIRST
+// maximum in TF scan order (a * kh + b, a over W) | (maximum > 0) << 2 — from the window's packed bf16 rows, i.e. compared on the values a
+// storing forward pass writes, with the comparisons maxpool_bwd_kernel makes on the stored tensor.
+template <int CNT>
+__device__ __forceinline__ uint32_t pool_code_word(const u32x4 (&rows)[CNT]) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        float v[CNT];
+#pragma unroll
+        for (int e = 0; e < CNT; ++e) {
+            const uint32_t pr = c < 2 ? rows[e].x : c < 4 ? rows[e].y : c < 6 ? rows[e].z : rows[e].w;
+            v[e] = (c & 1) ? bf_hi(pr) : bf_lo(pr);
+        }
+        int best = 0; float bv = v[0];
+#pragma unroll
+        for (int e = 1; e < CNT; ++e) if (v[e] > bv) { bv = v[e]; best = e; }
+        word |= (uint32_t)(best | ((bv > 0.f) ? 4 : 0)) << (4 * c);
+    }
+    return word;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -43,6 +43,7 @@ struct K3Args {
     // pool_kind 4 (a data gradient whose producer is a batch-norm + ReLU layer): the stored values are g = mask(y > 0) * result, and `pool` receives
     // the partial sums of the batch-norm BACKWARD pass per tile: [M / 256][2][N] = (sum g, sum g * xhat), xhat = (bnz - bn_mean) * bn_rstd
     const bf16_t* bnz; const float* bn_mean; const float* bn_rstd;
+    uint32_t* codes;                      // CODES instances (pool_kind 1 / 2): the pool's routing codes [pooled pixels][N / 8]; `out` may then be NULL
 };
 
 #ifdef OCR_EXPERIMENTS
@@ -85,7 +86,9 @@ template <int FM /* 16-pixel fragments per wave: 8 or 4 */, int BN /* channels p
                                interior boundary column, local column c at plane row 1 + c + k(c), k(c) = boundaries in [1, c]; the fragment
                                base is then a lane register per (dw, column block) */,
           bool BNB = false /* pool_kind 4 (batch-norm backward sums in the write-out): its own instances — compiled into the common epilogue its
-                              48 extra live registers spilled in the 256 x 128 kernels */>
+                              48 extra live registers spilled in the 256 x 128 kernels */,
+          bool CODES = false /* a fused pool in a training step: the pool write-out also stores the windows' routing codes (pool_code_word), and the
+                                full-resolution rows are not stored when `out` is NULL — its own instances, the common epilogue is unchanged */>
 __device__ __forceinline__ void k3_body(const K3Args& g) {
     constexpr int NW = 8, FN = 4, BM = 256;
     constexpr int WN = BN / 64, WMW = 4 / WN;           // waves along channels / pixels (per K half)
@@ -383,7 +386,7 @@ __device__ __forceinline__ void k3_body(const K3Args& g) {
                     if (!(bf_lo(q.w) > 0.f)) v.w &= 0xffff0000u;
                     if (!(bf_hi(q.w) > 0.f)) v.w &= 0x0000ffffu;
                 }
-                *(u32x4*)(g.out + ((long)m0 + lp) * g.N + n0 + u * 8) = v;
+                if (!CODES || g.out != nullptr) *(u32x4*)(g.out + ((long)m0 + lp) * g.N + n0 + u * 8) = v;
                 if (!BNB && g.pool_kind == 3) {          // statistics of what is stored: the bf16 values, as a separate pass over the tensor would see them
                     const float f[8] = {bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y), bf_lo(v.z), bf_hi(v.z), bf_lo(v.w), bf_hi(v.w)};
 #pragma unroll
@@ -427,12 +430,18 @@ __device__ __forceinline__ void k3_body(const K3Args& g) {
                     else { cl = 2 * (q / (H >> 1)); lp0 = cl * H + 2 * (q % (H >> 1)); }
                     const unsigned char* r0 = smem + lp0 * ROWB;
                     const int u0 = (u ^ ((cl & SWM) << 1)) << 4;
-                    u32x4 m = k3_max8(*(const u32x4*)(r0 + u0), *(const u32x4*)(r0 + ROWB + u0));
+                    u32x4 win[4] = {*(const u32x4*)(r0 + u0), *(const u32x4*)(r0 + ROWB + u0)};      // scan order: column (W) outer, feature row inner
+                    u32x4 m = k3_max8(win[0], win[1]);
                     if (kind == 2) {
                         const int u1 = (u ^ (((cl + 1) & SWM) << 1)) << 4;
-                        m = k3_max8(m, k3_max8(*(const u32x4*)(r0 + H * ROWB + u1), *(const u32x4*)(r0 + (H + 1) * ROWB + u1)));
+                        win[2] = *(const u32x4*)(r0 + H * ROWB + u1); win[3] = *(const u32x4*)(r0 + (H + 1) * ROWB + u1);
+                        m = k3_max8(m, k3_max8(win[2], win[3]));
                     }
                     *(u32x4*)(g.pool + (pbase + q) * g.N + n0 + u * 8) = m;
+                    if (CODES) {
+                        const u32x4 pair[2] = {win[0], win[1]};
+                        g.codes[(pbase + q) * (g.N >> 3) + (n0 >> 3) + u] = kind == 2 ? pool_code_word(win) : pool_code_word(pair);
+                    }
                 }
             }
             return;
@@ -488,6 +497,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int FM, int BN, int NST, int H, bool GENW>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_k3b_kernel(K3Args g) { k3_body<FM, BN, NST, H, false, GENW, true>(g); }
 
+// ... and with the fused pool's routing codes (aligned widths)
+template <int FM, int BN, int NST, int H, bool SINGLE>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_k3c_kernel(K3Args g) { k3_body<FM, BN, NST, H, SINGLE, false, false, true>(g); }
+
 template <int FM, int BN, int NST, int H, bool GENW>
 static int run_k3b(const K3Args& g, hipStream_t stream) {
     constexpr int PS = (256 / H + 2 + 7) / 8 * 8, PPIECES = (H * PS / 8 + 7) / 8 * 8;
@@ -508,6 +521,16 @@ static int run_k3(const K3Args& g, hipStream_t stream) {
     static_assert(lds <= 163840, "LDS");
     static_assert(256 * BN * 2 + 2 * (512 / (BN / 8)) * BN * 4 <= lds, "staged image + the statistics scratch behind it");
     const int mt = g.M / 256, nt = (g.N + BN - 1) / BN;
+    if (g.codes) {                               // the routing-code instances: a fused pool, aligned widths (conv3x3_pool_codes' coverage)
+        if constexpr (GENW) return OCR_ERR_INVALID;
+        else {
+            if ((g.pool_kind != 1 && g.pool_kind != 2) || (g.N & 63)) return OCR_ERR_INVALID;
+            if (ocr_allow_lds<conv_k3c_kernel<FM, BN, NST, H, SINGLE>>(lds) != hipSuccess) return OCR_ERR_EXEC;
+            conv_k3c_kernel<FM, BN, NST, H, SINGLE><<<mt * nt, 512, lds, stream>>>(g);
+            OCR_CHECK_LAUNCH();
+            return OCR_OK;
+        }
+    }
     if constexpr (GENW) {
         if (ocr_allow_lds<conv_k3w_kernel<FM, BN, NST, H>>(lds) != hipSuccess) return OCR_ERR_EXEC;
         conv_k3w_kernel<FM, BN, NST, H><<<mt * nt, 512, lds, stream>>>(g);
@@ -522,7 +545,7 @@ static int run_k3(const K3Args& g, hipStream_t stream) {
 // the instances: tile 'A' = 256 pixels x 128 channels, 'D' = 256 x 64; H and the forms as conv3x3_plan's plan_k3 chose them
 int launch_k3(const ConvPlan& p, const ConvOperands& o, hipStream_t stream) {
     const K3Args g = {(const bf16_t*)o.x, (const bf16_t*)o.wpack, p.M, p.Cout, p.Cin, p.W, p.H, (bf16_t*)o.y, o.bias, (const bf16_t*)o.mask,
-                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.prio, (const bf16_t*)o.bnz, o.bn_mean, o.bn_rstd};
+                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.prio, (const bf16_t*)o.bnz, o.bn_mean, o.bn_rstd, (uint32_t*)o.codes};
     const int H = p.H;
     const bool A = p.tile == 'A';
     if (p.epi_kind == CONV_EPI_BNBWD) {

@@ -45,6 +45,8 @@ struct ConvOperands {
     const float* bias; const void* mask;
     void* pool;                                  // CONV_EPI_POOL*: pooled bf16 output; CONV_EPI_STATS / _BNBWD: float partials
     const void* bnz; const float* bn_mean; const float* bn_rstd;   // CONV_EPI_BNBWD: the producer's pre-normalisation output and statistics
+    void* codes;                                 // CONV_EPI_POOL* on conv_ws / conv_k3 (ocr_conv3x3_pool_codes_supported): the pool's routing codes
+                                                 // uint32 [pooled pixels][Cout / 8]; y may then be NULL (no full-resolution output)
 };
 int launch_halo(const ConvPlan& p, const ConvOperands& o, hipStream_t stream);
 int launch_k2(const ConvPlan& p, const ConvOperands& o, hipStream_t stream);

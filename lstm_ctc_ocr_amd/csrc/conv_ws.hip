@@ -34,6 +34,7 @@ struct WsArgs {
     bf16_t* out; const float* bias; const bf16_t* mask; int flags;
     bf16_t* pool; int pool_kind;          // 0 none, 1 feature pairs (1 x 2), 2 2 x 2 (post-ReLU values of the stored tensor)
     int ntiles, slots, per_slot, xcd_map; // channel tiles; pixel-tile slots (workgroups per channel tile); pixel tiles per slot; XCD-aware id map
+    uint32_t* codes;                      // CODES instances: the fused pool's routing codes [pooled pixels][N / 8]; `out` may then be NULL (no full-resolution store)
 };
 
 typedef __attribute__((address_space(3))) void* ws_lptr_t;
@@ -69,6 +70,35 @@ __device__ __forceinline__ u32x4 ws_max8(u32x4 a, u32x4 b) {
     return r;
 }
 
+// The routing codes of a pool window (nn_ops.hip's pool_code_word: 4 bits per channel, index of the FIRST maximum in scan order | (maximum > 0)
+// << 2) in packed 16-bit integer arithmetic, two channels per instruction: the window holds post-ReLU values, i.e. bit patterns 0 .. 0x7FFF that
+// order like the floats (see ws_max2; NaN as there), so "first maximum" is the first element equal to the integer maximum.  ne[e] = min(m -
+// p[e], 1) is 0 where element e is a maximum; the index of the first such e is ne0 * (1 + ne1 * (1 + ne2)) (two elements: ne0).
+typedef unsigned short ws_u16x2 __attribute__((ext_vector_type(2)));
+template <int CNT>
+__device__ __forceinline__ uint32_t ws_code2(const uint32_t (&p)[CNT]) {      // -> the two channels' codes at bits 0-2 and 16-18
+    const ws_u16x2 one = {1, 1};
+    ws_u16x2 v[CNT];
+#pragma unroll
+    for (int e = 0; e < CNT; ++e) v[e] = __builtin_bit_cast(ws_u16x2, p[e]);
+    ws_u16x2 m = v[0];
+#pragma unroll
+    for (int e = 1; e < CNT; ++e) m = __builtin_elementwise_max(m, v[e]);
+    ws_u16x2 t = __builtin_elementwise_min((ws_u16x2)(m - v[CNT - 2]), one);
+#pragma unroll
+    for (int e = CNT - 3; e >= 0; --e) t = __builtin_elementwise_min((ws_u16x2)(m - v[e]), one) * (ws_u16x2)(t + one);
+    const ws_u16x2 code = t + (ws_u16x2)(__builtin_elementwise_min(m, one) << (ws_u16x2){2, 2});
+    return __builtin_bit_cast(uint32_t, code);
+}
+template <int CNT>
+__device__ __forceinline__ uint32_t ws_code_word(const u32x4 (&p)[CNT]) {     // eight channels -> one word, channel c at bits 4c .. 4c + 2
+    uint32_t x[CNT], y[CNT], z[CNT], w[CNT];
+#pragma unroll
+    for (int e = 0; e < CNT; ++e) { x[e] = p[e].x; y[e] = p[e].y; z[e] = p[e].z; w[e] = p[e].w; }
+    const uint32_t c0 = ws_code2(x), c1 = ws_code2(y), c2 = ws_code2(z), c3 = ws_code2(w);
+    return ((c0 | (c0 >> 12)) & 0xffu) | (((c1 | (c1 >> 12)) & 0xffu) << 8) | (((c2 | (c2 >> 12)) & 0xffu) << 16) | ((c3 | (c3 >> 12)) << 24);
+}
+
 // geometry of an instance — mirrored by tools/ws_plane_model.py (tests/test_ws_plane_model.py replays the index algebra on the CPU)
 template <int H, int NC, int KSPLIT>
 struct WsCfg {
@@ -97,7 +127,9 @@ struct WsCfg {
     static_assert(((H + 1) * PS) * 128 < 65536, "ds_read immediates");
 };
 
-template <int H, int NC, int KSPLIT, bool MASK /* the ReLU mask of the layer below is applied in the write-out (data gradients) */>
+template <int H, int NC, int KSPLIT, bool MASK /* the ReLU mask of the layer below is applied in the write-out (data gradients) */,
+          bool CODES = false /* forward with a fused pool in a training step: the pool write-out also stores the windows' routing codes, and the
+                                full-resolution store is skipped when `out` is NULL — instances of their own, the plain write-out is unchanged */>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_ws_kernel(WsArgs g) {
     using G = WsCfg<H, NC, KSPLIT>;
     constexpr int CF = G::CF, HF = G::HF, PS = G::PS, PI = G::PI, HWE = G::HWE, NPE = G::NPE;
@@ -347,29 +379,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (one wave: its own LDS writes are in order; nothing to wait for but the compiler's view)
             u32x4 val[NIT], mkv[MASK ? NIT : 1];
+            if (!CODES || g.out != nullptr) {       // (a codes launch without `out`: nothing reads the full-resolution tensor)
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int idx = it * 64 + lane, row = idx >> 3, u = idx & 7;
-                val[it] = *(const u32x4*)(S + row * 128 + ((u ^ (((row / HWE) & 3) << 1)) << 4));
-                if (has_mask) mkv[it] = *(const u32x4*)(smem + G::MOFF + wave * G::STW + idx * 16);
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int idx = it * 64 + lane, row = idx >> 3, u = idx & 7;
-                u32x4 v = val[it];
-                if (has_mask) {
-                    const u32x4 q = mkv[it];
-                    if (!(bf_lo(q.x) > 0.f)) v.x &= 0xffff0000u;
-                    if (!(bf_hi(q.x) > 0.f)) v.x &= 0x0000ffffu;
-                    if (!(bf_lo(q.y) > 0.f)) v.y &= 0xffff0000u;
-                    if (!(bf_hi(q.y) > 0.f)) v.y &= 0x0000ffffu;
-                    if (!(bf_lo(q.z) > 0.f)) v.z &= 0xffff0000u;
-                    if (!(bf_hi(q.z) > 0.f)) v.z &= 0x0000ffffu;
-                    if (!(bf_lo(q.w) > 0.f)) v.w &= 0xffff0000u;
-                    if (!(bf_hi(q.w) > 0.f)) v.w &= 0x0000ffffu;
+                for (int it = 0; it < NIT; ++it) {
+                    const int idx = it * 64 + lane, row = idx >> 3, u = idx & 7;
+                    val[it] = *(const u32x4*)(S + row * 128 + ((u ^ (((row / HWE) & 3) << 1)) << 4));
+                    if (has_mask) mkv[it] = *(const u32x4*)(smem + G::MOFF + wave * G::STW + idx * 16);
                 }
-                const long m = (long)(col0 + row / HWE) * H + h_lo + row % HWE;
-                *(u32x4*)(g.out + m * N + n0 + u * 8) = v;
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int idx = it * 64 + lane, row = idx >> 3, u = idx & 7;
+                    u32x4 v = val[it];
+                    if (has_mask) {
+                        const u32x4 q = mkv[it];
+                        if (!(bf_lo(q.x) > 0.f)) v.x &= 0xffff0000u;
+                        if (!(bf_hi(q.x) > 0.f)) v.x &= 0x0000ffffu;
+                        if (!(bf_lo(q.y) > 0.f)) v.y &= 0xffff0000u;
+                        if (!(bf_hi(q.y) > 0.f)) v.y &= 0x0000ffffu;
+                        if (!(bf_lo(q.z) > 0.f)) v.z &= 0xffff0000u;
+                        if (!(bf_hi(q.z) > 0.f)) v.z &= 0x0000ffffu;
+                        if (!(bf_lo(q.w) > 0.f)) v.w &= 0xffff0000u;
+                        if (!(bf_hi(q.w) > 0.f)) v.w &= 0x0000ffffu;
+                    }
+                    const long m = (long)(col0 + row / HWE) * H + h_lo + row % HWE;
+                    *(u32x4*)(g.out + m * N + n0 + u * 8) = v;
+                }
             }
             if (g.pool_kind == 1) {             // feature pairs (h, h + 1) of a column -> pooled row m / 2
                 constexpr int NQ = NC * (HWE / 2), PIT = NQ * 8 / 64;
@@ -386,6 +420,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     const int idx = it * 64 + lane, q = idx >> 3, u = idx & 7, col = q / (HWE / 2), ph = q % (HWE / 2);
                     const long pm = (long)(col0 + col) * (H / 2) + (h_lo >> 1) + ph;
                     *(u32x4*)(g.pool + pm * N + n0 + u * 8) = ws_max8(p0[it], p1[it]);
+                    if (CODES) { const u32x4 win[2] = {p0[it], p1[it]}; g.codes[pm * (N >> 3) + (n0 >> 3) + u] = ws_code_word(win); }
                 }
             } else if (g.pool_kind == 2) {      // 2 x 2 window of columns (2c, 2c + 1) x rows (2p, 2p + 1)
                 constexpr int NQ = (NC / 2) * (HWE / 2), PIT = NQ * 8 / 64;
@@ -404,6 +439,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                     const int idx = it * 64 + lane, q = idx >> 3, u = idx & 7, pc = q / (HWE / 2), ph = q % (HWE / 2);
                     const long pm = (long)((col0 >> 1) + pc) * (H / 2) + (h_lo >> 1) + ph;
                     *(u32x4*)(g.pool + pm * N + n0 + u * 8) = ws_max8(ws_max8(p0[it], p1[it]), ws_max8(p2[it], p3[it]));
+                    if (CODES) {    // scan order a * 2 + b: a over the columns (W), b over the feature rows
+                        const u32x4 win[4] = {p0[it], p1[it], p2[it], p3[it]};
+                        g.codes[pm * (N >> 3) + (n0 >> 3) + u] = ws_code_word(win);
+                    }
                 }
             }
         };
@@ -418,23 +457,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (clk && blockIdx.x == 0 && tid == 0) ocr_clk_exit(clk);
 }
 
-template <int H, int NC, int KSPLIT, bool MASK>
+template <int H, int NC, int KSPLIT, bool MASK, bool CODES = false>
 static int launch_ws_(const WsArgs& g, int grid, hipStream_t stream) {
     using G = WsCfg<H, NC, KSPLIT>;
     constexpr int lds = MASK ? G::LDS_MASK : G::LDS_PLAIN;
-    if (ocr_allow_lds<conv_ws_kernel<H, NC, KSPLIT, MASK>>(lds) != hipSuccess) return OCR_ERR_EXEC;
-    conv_ws_kernel<H, NC, KSPLIT, MASK><<<grid, 256, lds, stream>>>(g);
+    if (ocr_allow_lds<conv_ws_kernel<H, NC, KSPLIT, MASK, CODES>>(lds) != hipSuccess) return OCR_ERR_EXEC;
+    conv_ws_kernel<H, NC, KSPLIT, MASK, CODES><<<grid, 256, lds, stream>>>(g);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
 template <int H, int NC, int KSPLIT>
 static int launch_ws(const WsArgs& g, int grid, hipStream_t stream) {
+    if (g.codes) return (g.flags & WS_MASK) || !g.pool_kind ? OCR_ERR_INVALID : launch_ws_<H, NC, KSPLIT, false, true>(g, grid, stream);
     return (g.flags & WS_MASK) ? launch_ws_<H, NC, KSPLIT, true>(g, grid, stream) : launch_ws_<H, NC, KSPLIT, false>(g, grid, stream);
 }
 // instances: (H, Cin) = (16, 64), (16, 128), (8, 128); conv3x3_plan's plan_ws chooses them and sizes the persistent grid
 int launch_ws(const ConvPlan& p, const ConvOperands& o, hipStream_t stream) {
     const WsArgs g = {(const bf16_t*)o.x, (const bf16_t*)o.wpack, p.M, p.Cout, p.Cin, p.W, p.H, (bf16_t*)o.y, o.bias, (const bf16_t*)o.mask,
-                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.Cout / 64, p.slots, p.per_slot, p.xcd_map};
+                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.Cout / 64, p.slots, p.per_slot, p.xcd_map, (uint32_t*)o.codes};
     if (p.H == 16 && p.ws_ksplit == 1) return launch_ws<16, 16, 1>(g, p.grid, stream);
     if (p.H == 16) return launch_ws<16, 8, 2>(g, p.grid, stream);
     return launch_ws<8, 16, 2>(g, p.grid, stream);

@@ -588,3 +588,20 @@ extern "C" int ocr_conv3x3_relu_pool_bf16(const void* x, const void* wpack, void
     const ConvPlan p = conv3x3_plan(Nb * W * H, W, H, Cin, Cout, EPI_BIAS | EPI_RELU, conv3x3_pool_kind(kw, kh));
     return conv3x3_launch(p, {x, wpack, y, bias, nullptr, pooled}, (hipStream_t)stream);
 }
+// The training form of that launch: the pool's routing codes — uint32 [Nb * W/kw * H/kh][Cout / 8], 4 bits per channel: index of the window's
+// first maximum in TF scan order | (maximum > 0) << 2, compared on the bf16 values of y (ocr_maxpool_bwd_codes routes the gradient with them,
+// bit-identical to ocr_maxpool_bwd on y) — are written by the same epilogue, and y may be NULL: then the full-resolution tensor is not stored
+// at all.  Only conv_ws and the aligned-width conv_k3 instances have the form: ocr_conv3x3_pool_codes_supported tells whether the kernel planned
+// for the shape does (0: run ocr_conv3x3_relu_pool_bf16 and keep y for ocr_maxpool_bwd).
+static bool conv3x3_plan_has_codes(const ConvPlan& p) { return p.family == CONV_WS || (p.family == CONV_K3 && !p.genw); }
+extern "C" int ocr_conv3x3_pool_codes_supported(int Nb, int W, int H, int Cin, int Cout, int kw, int kh) {
+    const int kind = conv3x3_pool_kind(kw, kh);
+    return kind && conv3x3_plan_has_codes(conv3x3_plan(conv3x3_pixels(Nb, W, H, Cin, Cout), W, H, Cin, Cout, EPI_BIAS | EPI_RELU, kind));
+}
+extern "C" int ocr_conv3x3_relu_pool_codes_bf16(const void* x, const void* wpack, void* y, void* pooled, void* codes, int Nb, int W, int H,
+                                                int Cin, int Cout, const float* bias, int kw, int kh, void* stream) {
+    if (!x || !wpack || !pooled || !codes || ((size_t)codes & 3) || !bias || !ocr_conv3x3_pool_codes_supported(Nb, W, H, Cin, Cout, kw, kh))
+        return OCR_ERR_INVALID;
+    const ConvPlan p = conv3x3_plan(Nb * W * H, W, H, Cin, Cout, EPI_BIAS | EPI_RELU, conv3x3_pool_kind(kw, kh));
+    return conv3x3_launch(p, {x, wpack, y, bias, nullptr, pooled, nullptr, nullptr, nullptr, codes}, (hipStream_t)stream);
+}

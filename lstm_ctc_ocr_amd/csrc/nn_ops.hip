@@ -594,6 +594,44 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const bf16_t* __restri
     }
 }
 
+// maxpool_bwd_kernel from the routing codes the forward pass saved (codes[window][C / 8], common.h's pool_code_word) instead of the full-resolution
+// tensor: the same thread layout, the same decisions (first maximum; relu_mask: the winner's value > 0 = bit 2), bit-identical dx.
+template <int KW, int KH>
+__global__ __launch_bounds__(256) void maxpool_bwd_codes_kernel(const uint32_t* __restrict__ codes, const bf16_t* __restrict__ dy,
+                                                                bf16_t* __restrict__ dx, int Nb, int W, int H, int C,
+                                                                int relu_mask) {
+    constexpr int kw = KW, kh = KH;
+    const int Wo = W / kw, Ho = H / kh, groups = C >> 3;
+    const long total = (long)Nb * Wo * Ho * groups;   // one thread per output window x channel group
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        int gq = (int)(idx % groups);
+        long op = idx / groups;
+        int ho = (int)(op % Ho);
+        long q = op / Ho;
+        int wo = (int)(q % Wo);
+        long n = q / Wo;
+        long boff = (((n * W + (long)wo * kw) * H) + (long)ho * kh) * C + gq * 8;
+        const uint32_t word = codes[idx];
+        float g[8];
+        unpack8(*(const u32x4*)(dy + op * C + gq * 8), g);
+        if (relu_mask) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) if (!((word >> (4 * c)) & 4u)) g[c] = 0.f;
+        }
+#pragma unroll
+        for (int a = 0; a < kw; ++a)
+#pragma unroll
+            for (int b = 0; b < kh; ++b) {
+                const int cnt = a * kh + b;
+                float o[8];
+#pragma unroll
+                for (int c = 0; c < 8; ++c) o[c] = (((word >> (4 * c)) & 3u) == (uint32_t)cnt) ? g[c] : 0.f;
+                u32x4 pk = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]), pack_bf2(o[4], o[5]), pack_bf2(o[6], o[7])};
+                *(u32x4*)(dx + boff + ((long)a * H + b) * C) = pk;
+            }
+    }
+}
+
 // ============================================================================================
 // training-mode batch norm over rows of x[M][C] (bf16), biased variance, eps (TF contrib default 1e-3)
 //   reference: tf.contrib.layers.batch_norm(..., is_training=True)  network.py:176-178  (always batch stats)
@@ -730,10 +768,12 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict_
 // pass 3 with the max-pool that follows the layer (LSTM_train.py:33: conv4_2 -> max_pool 1 x 2 over the feature axis = row pairs (2q, 2q + 1)
 // of the [M][C] view): y is written as by bn_apply_kernel (the backward pass needs it) AND pooled[q] = max(y[2q], y[2q + 1]) — bf16 max of the
 // rounded values, i.e. bit-identical to maxpool_fwd_kernel<1, 2> on the stored tensor.  A thread keeps one channel group and walks PAIRS.
+// codes != NULL (training): the pair's routing codes (pool_code_word: which row is the first maximum, maximum > 0) are written INSTEAD of y —
+// all that the backward passes take from y when this pool is the layer's only consumer (bn_pool_route_codes).
 __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, bf16_t* __restrict__ pooled,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            long M, int C, int relu, int pairs_per_block) {
+                                                            long M, int C, int relu, int pairs_per_block, uint32_t* __restrict__ codes) {
     const int groups = C >> 3;
     const int rl = threadIdx.x / groups, gq = threadIdx.x % groups, rlanes = 256 / groups;
     if (rl >= rlanes) return;
@@ -757,9 +797,10 @@ __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const bf16_t* __rest
                 if (relu) o[c] = fmaxf(o[c], 0.f);
             }
             pk[e] = (u32x4){pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]), pack_bf2(o[4], o[5]), pack_bf2(o[6], o[7])};
-            *(u32x4*)(y + (2 * q + e) * C + gq * 8) = pk[e];
+            if (codes == nullptr) *(u32x4*)(y + (2 * q + e) * C + gq * 8) = pk[e];
         }
         *(u32x4*)(pooled + q * C + gq * 8) = max8(pk[0], pk[1]);
+        if (codes != nullptr) codes[q * groups + gq] = pool_code_word(pk);
     }
 }
 // The gradient of row r when the layer's consumer is that 1 x 2 max-pool and dy holds the POOLED gradient [M / 2][C]: the pool routes
@@ -776,11 +817,28 @@ __device__ __forceinline__ void bn_pool_route(const bf16_t* __restrict__ y, cons
         if (!win) g[c] = 0.f;
     }
 }
+// ... from the codes bn_apply_pool_kernel saved: one word instead of two rows of y.  Bit 0 names the winning row of the pair, bit 2 is the
+// ReLU mask of the winner (a losing row's gradient is zero whatever its own mask says): the decisions bn_pool_route + (y > 0) take on y.
+__device__ __forceinline__ void bn_pool_route_codes(const uint32_t* __restrict__ codes, const bf16_t* __restrict__ dp, long r, int C, int gq,
+                                                    int relu, float (&g)[8]) {
+    const uint32_t word = codes[(r >> 1) * (C >> 3) + gq];
+    unpack8(*(const u32x4*)(dp + (r >> 1) * C + gq * 8), g);
+    const uint32_t odd = (uint32_t)(r & 1);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const uint32_t code = word >> (4 * c);
+        if ((code & 1u) != odd || (relu && !(code & 4u))) g[c] = 0.f;
+    }
+}
 // backward pass 1: dz = dy * (y > 0) [if relu]; part[block][0][C] = sum dz, part[block][1][C] = sum dz * xhat over the block's rows
+// CODES (both backward passes): the pooled gradient is routed and masked from the forward pass's codes, y is not read — instances of their own:
+// as a run-time branch of the common kernels it cost the 35 small layers of the ResNet configuration 0.3-0.4 us per launch.
+template <bool CODES>
 __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ y,
                                                            const bf16_t* __restrict__ dy, const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, float* __restrict__ part,
-                                                           long M, int C, int rows_per_block, int relu, int pooled) {
+                                                           long M, int C, int rows_per_block, int relu, int pooled,
+                                                           const uint32_t* __restrict__ codes) {
     const int groups = C >> 3;
     const int rl = threadIdx.x / groups, gq = threadIdx.x % groups, rlanes = 256 / groups;
     const long r0 = (long)blockIdx.x * rows_per_block, r1 = min(M, r0 + rows_per_block);
@@ -792,12 +850,15 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const bf16_t* __restr
         for (long r = r0 + rl; r < r1; r += rlanes) {
             float xv[8], yv[8], g[8];
             unpack8(*(const u32x4*)(x + r * C + gq * 8), xv);
-            if (relu || pooled) unpack8(*(const u32x4*)(y + r * C + gq * 8), yv);
-            if (pooled) bn_pool_route(y, dy, r, C, gq, yv, g);        // dy = the pooled gradient [M / 2][C]
-            else unpack8(*(const u32x4*)(dy + r * C + gq * 8), g);
-            if (relu) {
+            if constexpr (CODES) bn_pool_route_codes(codes, dy, r, C, gq, relu, g);       // routes and masks: y is not read
+            else {
+                if (relu || pooled) unpack8(*(const u32x4*)(y + r * C + gq * 8), yv);
+                if (pooled) bn_pool_route(y, dy, r, C, gq, yv, g);        // dy = the pooled gradient [M / 2][C]
+                else unpack8(*(const u32x4*)(dy + r * C + gq * 8), g);
+                if (relu) {
 #pragma unroll
-                for (int c = 0; c < 8; ++c) if (!(yv[c] > 0.f)) g[c] = 0.f;
+                    for (int c = 0; c < 8; ++c) if (!(yv[c] > 0.f)) g[c] = 0.f;
+                }
             }
 #pragma unroll
             for (int c = 0; c < 8; ++c) { s[c] += g[c]; sx[c] = fmaf(g[c], (xv[c] - mu[c]) * rs[c], sx[c]); }
@@ -819,12 +880,14 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
     }
 }
 // backward pass 2: dx = gamma*rstd*(dz - mean(dz) - xhat*mean(dz*xhat))   (per-thread channel group, as bn_apply_kernel)
+template <bool CODES>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ y,
                                                            const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
                                                            const float* __restrict__ gamma, const double* __restrict__ sums,
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                           long M, int C, int relu, int rows_per_block, int pooled) {
+                                                           long M, int C, int relu, int rows_per_block, int pooled,
+                                                           const uint32_t* __restrict__ codes) {
     const int groups = C >> 3;
     const int rl = threadIdx.x / groups, gq = threadIdx.x % groups, rlanes = 256 / groups;
     if (rl >= rlanes) return;
@@ -841,12 +904,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
     for (long r = r0 + rl; r < r1; r += rlanes) {
         float xv[8], yv[8], g[8], o[8];
         unpack8(*(const u32x4*)(x + r * C + gq * 8), xv);
-        if (relu || pooled) unpack8(*(const u32x4*)(y + r * C + gq * 8), yv);
-        if (pooled) bn_pool_route(y, dy, r, C, gq, yv, g);
-        else unpack8(*(const u32x4*)(dy + r * C + gq * 8), g);
-        if (relu) {
+        if constexpr (CODES) bn_pool_route_codes(codes, dy, r, C, gq, relu, g);
+        else {
+            if (relu || pooled) unpack8(*(const u32x4*)(y + r * C + gq * 8), yv);
+            if (pooled) bn_pool_route(y, dy, r, C, gq, yv, g);
+            else unpack8(*(const u32x4*)(dy + r * C + gq * 8), g);
+            if (relu) {
 #pragma unroll
-            for (int c = 0; c < 8; ++c) if (!(yv[c] > 0.f)) g[c] = 0.f;
+                for (int c = 0; c < 8; ++c) if (!(yv[c] > 0.f)) g[c] = 0.f;
+            }
         }
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -1519,6 +1585,21 @@ extern "C" int ocr_maxpool_bwd(const void* x, const void* dy, void* dx, int Nb, 
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
+// ocr_maxpool_bwd from the routing codes of the forward pass (uint32 [Nb * W/kw * H/kh][C / 8], 4 bits per channel: index of the first maximum
+// in TF scan order | (maximum > 0) << 2) instead of the pool's full-resolution input: bit-identical dx.  Windows (2, 2) and (1, 2).
+extern "C" int ocr_maxpool_bwd_codes(const void* codes, const void* dy, void* dx, int Nb, int W, int H, int C, int kw, int kh,
+                                     int relu_mask, void* stream) {
+    if (!codes || ((size_t)codes & 3) || !dy || !dx || (C & 7) || Nb <= 0 || W <= 0 || H <= 0 || kh != 2 || kw < 1 || kw > 2 || W % kw || H % kh)
+        return OCR_ERR_INVALID;
+    long total = (long)Nb * (W / kw) * (H / kh) * (C >> 3);
+    const uint32_t* ci = (const uint32_t*)codes; const bf16_t* dyi = (const bf16_t*)dy; bf16_t* dxo = (bf16_t*)dx;
+    hipStream_t st = (hipStream_t)stream;
+    int gr = grid_for(total, 8192);
+    if (kw == 2) maxpool_bwd_codes_kernel<2, 2><<<gr, 256, 0, st>>>(ci, dyi, dxo, Nb, W, H, C, relu_mask);
+    else maxpool_bwd_codes_kernel<1, 2><<<gr, 256, 0, st>>>(ci, dyi, dxo, Nb, W, H, C, relu_mask);
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}
 // workspace: ocr_bn_workspace_bytes(M, C) bytes = per-block partial rows (fp32) followed by 2*C doubles; not zeroed, no atomics
 extern "C" size_t ocr_bn_workspace_bytes(long M, int C) {
     if (M <= 0 || C <= 0) return 0;
@@ -1533,9 +1614,10 @@ extern "C" size_t ocr_bn_workspace_bytes(long M, int C) {
 static constexpr int bn_rows_per_thread() { return 4; }
 static int bn_train_fwd_impl(const void* x, void* y, const float* gamma, const float* beta, float* save_mean,
                              float* save_rstd, long M, int C, float eps, int relu, void* workspace, const void* residual,
-                             int partial_rows, void* pooled, void* stream_) {
+                             int partial_rows, void* pooled, void* codes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!x || !y || !gamma || !beta || !save_mean || !save_rstd || !workspace || (C & 7) || C > 2048 || M <= 0)
+    if (codes ? (!pooled || ((size_t)codes & 3)) : !y) return OCR_ERR_INVALID;      // the codes form writes no y
+    if (!x || !gamma || !beta || !save_mean || !save_rstd || !workspace || (C & 7) || C > 2048 || M <= 0)
         return OCR_ERR_INVALID;
     int rlanes = 256 / (C >> 3); if (rlanes < 1) return OCR_ERR_INVALID;
     if (partial_rows < 0 || (size_t)partial_rows * 2 * C * sizeof(float) > ocr_bn_workspace_bytes(M, C) - 2 * (size_t)C * sizeof(double)) return OCR_ERR_INVALID;
@@ -1564,7 +1646,7 @@ static int bn_train_fwd_impl(const void* x, void* y, const float* gamma, const f
     const int arows = bn_rows_per_thread() * rlanes;                // rows per block of the apply pass
     if (pooled)
         bn_apply_pool_kernel<<<ceil_div(M / 2, (long)(arows / 2)), 256, 0, stream>>>((const bf16_t*)x, (bf16_t*)y, (bf16_t*)pooled, save_mean, save_rstd,
-                                                                                       gamma, beta, M, C, relu, arows / 2);
+                                                                                       gamma, beta, M, C, relu, arows / 2, (uint32_t*)codes);
     else
         bn_apply_kernel<<<ceil_div(M, (long)arows), 256, 0, stream>>>((const bf16_t*)x, (bf16_t*)y, save_mean, save_rstd, gamma,
                                                                         beta, M, C, relu, arows, (const bf16_t*)residual);
@@ -1573,11 +1655,19 @@ static int bn_train_fwd_impl(const void* x, void* y, const float* gamma, const f
 }
 extern "C" int ocr_bn_train_fwd(const void* x, void* y, const float* gamma, const float* beta, float* save_mean,
                                 float* save_rstd, long M, int C, float eps, int relu, void* workspace, const void* residual, void* stream_) {
-    return bn_train_fwd_impl(x, y, gamma, beta, save_mean, save_rstd, M, C, eps, relu, workspace, residual, 0, nullptr, stream_);
+    return bn_train_fwd_impl(x, y, gamma, beta, save_mean, save_rstd, M, C, eps, relu, workspace, residual, 0, nullptr, nullptr, stream_);
 }
 extern "C" int ocr_bn_train_fwd2(const void* x, void* y, const float* gamma, const float* beta, float* save_mean, float* save_rstd, long M,
                                  int C, float eps, int relu, void* workspace, const void* residual, int partial_rows, void* pooled, void* stream_) {
-    return bn_train_fwd_impl(x, y, gamma, beta, save_mean, save_rstd, M, C, eps, relu, workspace, residual, partial_rows, pooled, stream_);
+    return bn_train_fwd_impl(x, y, gamma, beta, save_mean, save_rstd, M, C, eps, relu, workspace, residual, partial_rows, pooled, nullptr, stream_);
+}
+// ocr_bn_train_fwd2 with pooled != NULL whose apply pass writes the pool's routing codes (uint32 [M / 2][C / 8], the format of
+// ocr_maxpool_bwd_codes, window 1 x 2) INSTEAD of y (may be NULL): the training form where the pool is the layer's only consumer —
+// ocr_bn_train_bwd_codes takes from the codes what the backward passes would read from y.
+extern "C" int ocr_bn_train_fwd_codes(const void* x, const float* gamma, const float* beta, float* save_mean, float* save_rstd, long M, int C,
+                                      float eps, int relu, void* workspace, int partial_rows, void* pooled, void* codes, void* stream_) {
+    if (!codes) return OCR_ERR_INVALID;
+    return bn_train_fwd_impl(x, nullptr, gamma, beta, save_mean, save_rstd, M, C, eps, relu, workspace, nullptr, partial_rows, pooled, codes, stream_);
 }
 // pooled_dy: dy is the gradient of the 1 x 2 max-pool that consumes the layer ([M / 2][C]); both passes route it themselves (first maximum of
 // the row pair, bn_pool_route) instead of reading a full-resolution gradient that a max-pool backward pass wrote.
@@ -1585,9 +1675,10 @@ extern "C" int ocr_bn_train_fwd2(const void* x, void* y, const float* gamma, con
 // by the data-gradient kernel that produced it (ocr_conv3x3_dgrad_bnbwd_bf16): no statistics pass, and the apply pass reads neither y nor a mask.
 static int bn_train_bwd_impl(const void* x, const void* y, const void* dy, void* dx, const float* gamma,
                              const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta, long M,
-                             int C, int relu, void* workspace, int pooled_dy, int partial_rows, void* stream_) {
+                             int C, int relu, void* workspace, int pooled_dy, int partial_rows, const void* codes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!x || !y || !dy || !dx || !gamma || !save_mean || !save_rstd || !dgamma || !dbeta || !workspace || (C & 7) ||
+    if (codes ? (!pooled_dy || ((size_t)codes & 3)) : !y) return OCR_ERR_INVALID;      // the codes stand in for y
+    if (!x || !dy || !dx || !gamma || !save_mean || !save_rstd || !dgamma || !dbeta || !workspace || (C & 7) ||
         C > 2048 || M <= 0 || (pooled_dy && (M & 1)) || partial_rows < 0 || (partial_rows && pooled_dy))
         return OCR_ERR_INVALID;
     const int rpb = bn_rows_per_block_host(M, 512);
@@ -1609,28 +1700,39 @@ static int bn_train_bwd_impl(const void* x, const void* y, const void* dy, void*
     if (partial_rows > nblk) return OCR_ERR_INVALID;                 // the partial rows share the block rows' space in front of `sums`
     if (partial_rows) relu = 0;                                       // premasked
     else {
-        bn_bwd_stats_kernel<<<nblk, 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, save_mean,
-                                                      save_rstd, part, M, C, rpb, relu, pooled_dy);
+        if (codes) bn_bwd_stats_kernel<true><<<nblk, 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, save_mean,
+                                                                    save_rstd, part, M, C, rpb, relu, pooled_dy, (const uint32_t*)codes);
+        else bn_bwd_stats_kernel<false><<<nblk, 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, save_mean,
+                                                                   save_rstd, part, M, C, rpb, relu, pooled_dy, nullptr);
         OCR_CHECK_LAUNCH();
     }
     bn_bwd_finalize_kernel<<<ceil_div(C, 16), 256, 0, stream>>>(part, partial_rows ? partial_rows : nblk, sums, dgamma, dbeta, C);
     OCR_CHECK_LAUNCH();
     const int arows = bn_rows_per_thread() * (256 / (C >> 3));      // rows per block of the apply pass
-    bn_bwd_apply_kernel<<<ceil_div(M, (long)arows), 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy,
-                                                                        (bf16_t*)dx, save_mean, save_rstd, gamma,
-                                                                        sums, dgamma, dbeta, M, C, relu, arows, pooled_dy);
+    if (codes) bn_bwd_apply_kernel<true><<<ceil_div(M, (long)arows), 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy,
+                                                                                       (bf16_t*)dx, save_mean, save_rstd, gamma, sums, dgamma, dbeta,
+                                                                                       M, C, relu, arows, pooled_dy, (const uint32_t*)codes);
+    else bn_bwd_apply_kernel<false><<<ceil_div(M, (long)arows), 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy,
+                                                                                      (bf16_t*)dx, save_mean, save_rstd, gamma, sums, dgamma, dbeta,
+                                                                                      M, C, relu, arows, pooled_dy, nullptr);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
 extern "C" int ocr_bn_train_bwd(const void* x, const void* y, const void* dy, void* dx, const float* gamma,
                                 const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta, long M,
                                 int C, int relu, void* workspace, void* stream_) {
-    return bn_train_bwd_impl(x, y, dy, dx, gamma, save_mean, save_rstd, dgamma, dbeta, M, C, relu, workspace, 0, 0, stream_);
+    return bn_train_bwd_impl(x, y, dy, dx, gamma, save_mean, save_rstd, dgamma, dbeta, M, C, relu, workspace, 0, 0, nullptr, stream_);
 }
 extern "C" int ocr_bn_train_bwd2(const void* x, const void* y, const void* dy, void* dx, const float* gamma, const float* save_mean,
                                  const float* save_rstd, float* dgamma, float* dbeta, long M, int C, int relu, void* workspace,
                                  int pooled_dy, int partial_rows, void* stream_) {
-    return bn_train_bwd_impl(x, y, dy, dx, gamma, save_mean, save_rstd, dgamma, dbeta, M, C, relu, workspace, pooled_dy, partial_rows, stream_);
+    return bn_train_bwd_impl(x, y, dy, dx, gamma, save_mean, save_rstd, dgamma, dbeta, M, C, relu, workspace, pooled_dy, partial_rows, nullptr, stream_);
+}
+// ocr_bn_train_bwd2(pooled_dy = 1) from the codes of ocr_bn_train_fwd_codes instead of y: bit-identical dx, dgamma and dbeta.
+extern "C" int ocr_bn_train_bwd_codes(const void* x, const void* codes, const void* dy, void* dx, const float* gamma, const float* save_mean,
+                                      const float* save_rstd, float* dgamma, float* dbeta, long M, int C, int relu, void* workspace, void* stream_) {
+    if (!codes) return OCR_ERR_INVALID;
+    return bn_train_bwd_impl(x, nullptr, dy, dx, gamma, save_mean, save_rstd, dgamma, dbeta, M, C, relu, workspace, 1, 0, codes, stream_);
 }
 extern "C" int ocr_colsum_bf16(const void* a, float* out, long M, int C, long lda, void* stream) {
     if (!a || !out || (C & 7) || C > 2048 || M <= 0) return OCR_ERR_INVALID;

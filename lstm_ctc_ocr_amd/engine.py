@@ -170,7 +170,22 @@ class _ConvOp(_Op):
                 # pool routing + ReLU bits saved by the training forward pass (4 bits per pooled output) for the backward pass
                 sp.buf[self.key + '/codes'] = torch.empty((s[0] * (s[1] // 2) * (s[2] // 2), 8), dtype=torch.int32, device=dev)
             return
-        sp.buf[self.key + '/y'] = torch.empty(o, dtype=BF16, device=dev)
+        # A max-pool that is this layer's only consumer (bn_pool: behind the batch norm; pool_after: written by the convolution's epilogue): a
+        # training forward pass writes the pool's routing codes (4 bits per pooled output: which element of the window won, and its ReLU
+        # bit — conv1's format) instead of the full-resolution y, whose only readers were backward passes looking for exactly that
+        # (OCR_POOL_CODES=0: keep y).  No y buffer then: an inference forward on this plan allocates it on first use (_ConvOp.y).
+        windows = 0
+        if os.environ.get('OCR_POOL_CODES', '1') != '0':
+            p = self.pool_after
+            if self.bn_pool is not None:
+                windows = o[0] * o[1] * o[2] // 2
+            elif (p is not None and ops.conv3x3_pool_supported(s[0], s[1], s[2], self.ci, self.co, p.kw_t, p.kh_f)
+                    and ops.conv3x3_pool_codes_supported(s[0], s[1], s[2], self.ci, self.co, p.kw_t, p.kh_f)):
+                windows = o[0] * (o[1] // p.kw_t) * (o[2] // p.kh_f)
+        if windows:
+            sp.buf[self.key + '/pool_codes'] = torch.empty((windows, self.co // 8), dtype=torch.int32, device=dev)
+        else:
+            sp.buf[self.key + '/y'] = torch.empty(o, dtype=BF16, device=dev)
         sp.buf[self.key + '/dy'] = torch.empty(o, dtype=BF16, device=dev)
         if self.bn:
             sp.buf[self.key + '/z'] = torch.empty(o, dtype=BF16, device=dev)
@@ -236,6 +251,12 @@ class _ConvOp(_Op):
             elif need and (have is None or have.numel() < need):     # one buffer per plan, shared by all layers (one stream)
                 sp.buf['wgrad_ws'] = torch.empty(need, dtype=torch.uint8, device=dev)
 
+    def y(self, sp):
+        t = sp.buf.get(self.key + '/y')
+        if t is None:       # a plan whose training steps keep routing codes instead (alloc): an inference forward is the first to need it
+            t = sp.buf[self.key + '/y'] = torch.empty(sp.shape[self.key][1], dtype=BF16, device=self.eng.device)
+        return t
+
     def shadow_params(self):
         return [self.name + '/weights'] if self.kind in ('1x1', 'full') else []
 
@@ -263,7 +284,8 @@ class _ConvOp(_Op):
             sp.rings_ready = set(getattr(sp, 'lstm_sync_keys', ())) if ones is not None else set()
             sp.rings_armed = ones is not None         # (what the last forward pass did; rings_ready is consumed by the launches)
             return
-        y = self.y(sp)
+        codes = sp.buf.get(self.key + '/pool_codes') if e.training else None
+        y = None if codes is not None else self.y(sp)
         if self.kind == 'c1':
             ops.conv1_fwd(x, e.param(self.name + '/weights'), bias, relu=self.relu, out=y)
             return
@@ -271,7 +293,10 @@ class _ConvOp(_Op):
         relu_now = self.relu and not self.bn
         if self.kind == '3x3' and self.pool_after is not None and self.pool_after.key in sp.fused_pools:
             p = self.pool_after
-            ops.conv3x3_relu_pool(x, self.wpack.view(self.co, 3, 3, self.ci), y, p.y(sp), bias, p.kw_t, p.kh_f)
+            if codes is not None:
+                ops.conv3x3_relu_pool_codes(x, self.wpack.view(self.co, 3, 3, self.ci), None, p.y(sp), codes, bias, p.kw_t, p.kh_f)
+            else:
+                ops.conv3x3_relu_pool(x, self.wpack.view(self.co, 3, 3, self.ci), y, p.y(sp), bias, p.kw_t, p.kh_f)
         elif self.kind == '3x3' and self.bn and sp.bn_stat_rows[self.key]:
             ops.conv3x3_stats(x, self.wpack.view(self.co, 3, 3, self.ci), tgt, sp.buf[self.key + '/bnws'], bias=bias)
         elif self.kind == '3x3':
@@ -293,9 +318,9 @@ class _ConvOp(_Op):
             pooled = self.bn_pool.y(sp).view(M // 2, self.co) if self.bn_pool is not None else None
             ops.bn_train_fwd(tgt.view(M, self.co), e.param('%s/%s/gamma' % (self.name, self.name)),
                              e.param('%s/%s/beta' % (self.name, self.name)), BN_EPS, relu,
-                             sp.buf[self.key + '/bnws'], out=y.view(M, self.co),
+                             sp.buf[self.key + '/bnws'], out=None if y is None else y.view(M, self.co),
                              save_mean=sp.buf[self.key + '/mean'], save_rstd=sp.buf[self.key + '/rstd'], residual=res,
-                             partial_rows=sp.bn_stat_rows[self.key], pooled=pooled)
+                             partial_rows=sp.bn_stat_rows[self.key], pooled=pooled, codes=codes)
 
     def bwd(self, sp):
         e = self.eng
@@ -322,18 +347,19 @@ class _ConvOp(_Op):
         dz = dy
         if self.bn:
             dz = sp.buf[self.key + '/dz']
-            ymask, relu = self.y(sp), self.relu
+            codes = sp.buf.get(self.key + '/pool_codes')
+            ymask, relu = (self.y(sp) if codes is None else None), self.relu
             if self.mask_from is not None:          # gradient and ReLU mask straight from the residual add + relu behind this layer
                 dy, ymask, relu = self.mask_from.dy(sp), self.mask_from.y(sp), True
             dy2 = dy.view(M, self.co)
             if self.bn_pool is not None:            # the pooled gradient, routed by the passes themselves
                 dy2 = self.bn_pool.dy(sp).view(M // 2, self.co)
-            ops.bn_train_bwd(sp.buf[self.key + '/z'].view(M, self.co), ymask.view(M, self.co), dy2,
+            ops.bn_train_bwd(sp.buf[self.key + '/z'].view(M, self.co), None if ymask is None else ymask.view(M, self.co), dy2,
                              e.param('%s/%s/gamma' % (self.name, self.name)), sp.buf[self.key + '/mean'],
                              sp.buf[self.key + '/rstd'], e.grad('%s/%s/gamma' % (self.name, self.name)),
                              e.grad('%s/%s/beta' % (self.name, self.name)), relu, sp.buf[self.key + '/bnws'],
                              out=dz.view(M, self.co), pooled_dy=self.bn_pool is not None,
-                             partial_rows=getattr(sp, 'bn_bwd_rows', {}).get(self.key, 0))
+                             partial_rows=getattr(sp, 'bn_bwd_rows', {}).get(self.key, 0), codes=codes)
         dw = e.grad(self.name + '/weights')
         db = e.grad(self.name + '/biases') if self.biased else None
         if self.kind == 'c1':
@@ -449,7 +475,11 @@ class _PoolOp(_Op):
             return
         pdy, finish = self.eng.grad_dst(sp, self.prev)
         if pdy is not None:
-            ops.maxpool_bwd(self.prev.y(sp), self.dy(sp), self.kw_t, self.kh_f, self.prev.mask_in_consumer, out=pdy)
+            codes = sp.buf.get(self.prev.key + '/pool_codes') if getattr(self.prev, 'pool_after', None) is self else None
+            if codes is not None:       # the producing convolution's training forward left routing codes and no full-resolution output
+                ops.maxpool_bwd_codes(codes, self.dy(sp), self.kw_t, self.kh_f, self.prev.mask_in_consumer, out=pdy)
+            else:
+                ops.maxpool_bwd(self.prev.y(sp), self.dy(sp), self.kw_t, self.kh_f, self.prev.mask_in_consumer, out=pdy)
             finish()
 
 

@@ -150,6 +150,22 @@ def conv3x3_relu_pool(x, wpack, out, pooled, bias, kw, kh):
     return out, pooled
 
 
+def conv3x3_pool_codes_supported(Nb, W, H, Cin, Cout, kw, kh):
+    """Whether the kernel planned for this shape's conv3x3_relu_pool can also write the pool's routing codes (conv3x3_relu_pool_codes)."""
+    return bool(nat.lib().ocr_conv3x3_pool_codes_supported(Nb, W, H, Cin, Cout, kw, kh))
+
+
+def conv3x3_relu_pool_codes(x, wpack, out, pooled, codes, bias, kw, kh):
+    """conv3x3_relu_pool that also writes the pool's routing codes (int32 [Nb * W/kw * H/kh, Cout / 8], what maxpool_bwd_codes reads).  out may be
+    None: the full-resolution tensor is then not stored at all."""
+    Nb, W, H, Cin = x.shape
+    Cout = wpack.shape[0]
+    assert codes.dtype == torch.int32 and codes.numel() == Nb * (W // kw) * (H // kh) * (Cout // 8), (codes.dtype, tuple(codes.shape))
+    call("ocr_conv3x3_relu_pool_codes_bf16", ptr(_dev(x)), ptr(wpack), ptr(out), ptr(pooled), ptr(codes), Nb, W, H, Cin, Cout, ptr(bias),
+         kw, kh, _st())
+    return out, pooled, codes
+
+
 def gemm_tn(A, B, out, *, Mk=None, I=None, J=None, lda=None, ldb=None, ldo=None, row_group=0, row_skip=0,
             a_row_off=0, scale=1.0, splits=0, colsum=None):
     """out[I][J] (f32) += scale * A^T B;  colsum[J] += scale * column sums of B (bias gradient) when given."""
@@ -348,17 +364,39 @@ def maxpool_bwd(x, dy, kw, kh, relu_mask, out=None):
     return out
 
 
+def maxpool_bwd_codes(codes, dy, kw, kh, relu_mask, out=None):
+    """maxpool_bwd from the routing codes a training forward pass saved (int32 [Nb * W/kw * H/kh, C / 8]: 4 bits per channel, index of the
+    window's first maximum | (maximum > 0) << 2) instead of the pool's input; dy is the pooled gradient.  Bit-identical to maxpool_bwd."""
+    Nb, Wo, Ho, C = dy.shape
+    W, H = Wo * kw, Ho * kh
+    assert codes.dtype == torch.int32 and codes.numel() == Nb * Wo * Ho * (C // 8), (codes.dtype, tuple(codes.shape))
+    if out is None:
+        out = torch.empty((Nb, W, H, C), dtype=BF16, device=dy.device)
+    call("ocr_maxpool_bwd_codes", ptr(_dev(codes)), ptr(dy), ptr(out), Nb, W, H, C, kw, kh, int(relu_mask), _st())
+    return out
+
+
 def bn_workspace(M, C, device):
     """Scratch block for bn_train_fwd / bn_train_bwd on [M, C] (ocr_bn_workspace_bytes)."""
     return torch.empty(int(nat.lib().ocr_bn_workspace_bytes(int(M), int(C))), dtype=torch.uint8, device=device)
 
 
 def bn_train_fwd(x2d, gamma, beta, eps, relu, workspace, out=None, save_mean=None, save_rstd=None, residual=None, partial_rows=0,
-                 pooled=None):
+                 pooled=None, codes=None):
     """residual (bf16 [M, C]): out = [relu](bf16(bn(x)) + residual) — batch norm, add and relu of a residual block in one apply pass.
     partial_rows > 0: the workspace already holds that many partial statistics rows from the producing convolution (conv3x3_stats);
-    pooled (bf16 [M / 2, C]): the 1 x 2 max-pool over row pairs that follows the layer, written by the apply pass."""
+    pooled (bf16 [M / 2, C]): the 1 x 2 max-pool over row pairs that follows the layer, written by the apply pass.
+    codes (int32 [M / 2, C / 8], with pooled): the pool's routing codes are written INSTEAD of the full-resolution output (the returned `out`
+    is None) — bn_train_bwd(codes=...) needs nothing else of it."""
     M, C = x2d.shape
+    if codes is not None:
+        assert pooled is not None and residual is None and out is None
+        assert codes.dtype == torch.int32 and tuple(codes.shape) == (M // 2, C // 8), (codes.dtype, tuple(codes.shape))
+        if save_mean is None: save_mean = torch.empty(C, dtype=F32, device=x2d.device)
+        if save_rstd is None: save_rstd = torch.empty(C, dtype=F32, device=x2d.device)
+        call("ocr_bn_train_fwd_codes", ptr(_dev(x2d)), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_rstd), M, C,
+             float(eps), int(relu), ptr(workspace), int(partial_rows), ptr(pooled), ptr(codes), _st())
+        return None, save_mean, save_rstd
     if out is None: out = torch.empty_like(x2d)
     if save_mean is None: save_mean = torch.empty(C, dtype=F32, device=x2d.device)
     if save_rstd is None: save_rstd = torch.empty(C, dtype=F32, device=x2d.device)
@@ -371,11 +409,19 @@ def bn_train_fwd(x2d, gamma, beta, eps, relu, workspace, out=None, save_mean=Non
     return out, save_mean, save_rstd
 
 
-def bn_train_bwd(x2d, y2d, dy2d, gamma, save_mean, save_rstd, dgamma, dbeta, relu, workspace, out=None, pooled_dy=False, partial_rows=0):
+def bn_train_bwd(x2d, y2d, dy2d, gamma, save_mean, save_rstd, dgamma, dbeta, relu, workspace, out=None, pooled_dy=False, partial_rows=0,
+                 codes=None):
     """pooled_dy: dy2d is the gradient of the 1 x 2 max-pool behind the layer ([M / 2, C]); the passes route it themselves.
-    partial_rows > 0: dy2d is already ReLU-masked and the workspace holds that many partial rows from conv3x3_dgrad_bnbwd."""
+    partial_rows > 0: dy2d is already ReLU-masked and the workspace holds that many partial rows from conv3x3_dgrad_bnbwd.
+    codes (with pooled_dy; y2d may be None): what bn_train_fwd(codes=...) saved stands in for y2d."""
     M, C = x2d.shape
     if out is None: out = torch.empty_like(x2d)
+    if codes is not None:
+        assert pooled_dy and not partial_rows and tuple(dy2d.shape) == (M // 2, C)
+        assert codes.dtype == torch.int32 and tuple(codes.shape) == (M // 2, C // 8), (codes.dtype, tuple(codes.shape))
+        call("ocr_bn_train_bwd_codes", ptr(_dev(x2d)), ptr(codes), ptr(dy2d), ptr(out), ptr(gamma), ptr(save_mean), ptr(save_rstd),
+             ptr(dgamma), ptr(dbeta), M, C, int(relu), ptr(workspace), _st())
+        return out
     if pooled_dy or partial_rows:
         assert tuple(dy2d.shape) == ((M // 2, C) if pooled_dy else (M, C))
         call("ocr_bn_train_bwd2", ptr(_dev(x2d)), ptr(y2d), ptr(dy2d), ptr(out), ptr(gamma), ptr(save_mean), ptr(save_rstd),
