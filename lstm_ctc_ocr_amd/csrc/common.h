@@ -69,6 +69,33 @@ __device__ __forceinline__ uint32_t pool_code_word(const u32x4 (&rows)[CNT]) {
     return word;
 }
 
+// The same codes in packed 16-bit integer arithmetic, two channels per instruction, for windows of post-ReLU values: those are bit patterns
+// 0 .. 0x7F80 that order like the floats, so "first maximum" is the first element equal to the integer maximum.  p[e] = element e of the window
+// as a packed bf16 pair; ne[e] = min(m - p[e], 1) is 0 where element e is a maximum, and the index of the first such e is
+// ne0 * (1 + ne1 * (1 + ne2)) (two elements: ne0).  Returns the two channels' codes at bits 0-2 and 16-18 and leaves the window's packed maximum
+// (= the pooled output: rounding is monotone) in mx.
+typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+template <int CNT>
+__device__ __forceinline__ uint32_t pool_code2_u16(const uint32_t (&p)[CNT], uint32_t& mx) {
+    const u16x2_t one = {1, 1};
+    u16x2_t v[CNT];
+#pragma unroll
+    for (int e = 0; e < CNT; ++e) v[e] = __builtin_bit_cast(u16x2_t, p[e]);
+    u16x2_t m = v[0];
+#pragma unroll
+    for (int e = 1; e < CNT; ++e) m = __builtin_elementwise_max(m, v[e]);
+    u16x2_t t = __builtin_elementwise_min((u16x2_t)(m - v[CNT - 2]), one);
+#pragma unroll
+    for (int e = CNT - 3; e >= 0; --e) t = __builtin_elementwise_min((u16x2_t)(m - v[e]), one) * (u16x2_t)(t + one);
+    const u16x2_t code = t + (u16x2_t)(__builtin_elementwise_min(m, one) << (u16x2_t){2, 2});
+    mx = __builtin_bit_cast(uint32_t, m);
+    return __builtin_bit_cast(uint32_t, code);
+}
+// four such pairs -> one word, channel c at bits 4c .. 4c + 2
+__device__ __forceinline__ uint32_t pool_code2_merge(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+    return ((c0 | (c0 >> 12)) & 0xffu) | (((c1 | (c1 >> 12)) & 0xffu) << 8) | (((c2 | (c2 >> 12)) & 0xffu) << 16) | ((c3 | (c3 >> 12)) << 24);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -74,21 +74,10 @@ __device__ __forceinline__ u32x4 ws_max8(u32x4 a, u32x4 b) {
 // << 2) in packed 16-bit integer arithmetic, two channels per instruction: the window holds post-ReLU values, i.e. bit patterns 0 .. 0x7FFF that
 // order like the floats (see ws_max2; NaN as there), so "first maximum" is the first element equal to the integer maximum.  ne[e] = min(m -
 // p[e], 1) is 0 where element e is a maximum; the index of the first such e is ne0 * (1 + ne1 * (1 + ne2)) (two elements: ne0).
-typedef unsigned short ws_u16x2 __attribute__((ext_vector_type(2)));
 template <int CNT>
-__device__ __forceinline__ uint32_t ws_code2(const uint32_t (&p)[CNT]) {      // -> the two channels' codes at bits 0-2 and 16-18
-    const ws_u16x2 one = {1, 1};
-    ws_u16x2 v[CNT];
-#pragma unroll
-    for (int e = 0; e < CNT; ++e) v[e] = __builtin_bit_cast(ws_u16x2, p[e]);
-    ws_u16x2 m = v[0];
-#pragma unroll
-    for (int e = 1; e < CNT; ++e) m = __builtin_elementwise_max(m, v[e]);
-    ws_u16x2 t = __builtin_elementwise_min((ws_u16x2)(m - v[CNT - 2]), one);
-#pragma unroll
-    for (int e = CNT - 3; e >= 0; --e) t = __builtin_elementwise_min((ws_u16x2)(m - v[e]), one) * (ws_u16x2)(t + one);
-    const ws_u16x2 code = t + (ws_u16x2)(__builtin_elementwise_min(m, one) << (ws_u16x2){2, 2});
-    return __builtin_bit_cast(uint32_t, code);
+__device__ __forceinline__ uint32_t ws_code2(const uint32_t (&p)[CNT]) {      // -> the two channels' codes at bits 0-2 and 16-18 (common.h)
+    uint32_t mx;
+    return pool_code2_u16(p, mx);
 }
 template <int CNT>
 __device__ __forceinline__ uint32_t ws_code_word(const u32x4 (&p)[CNT]) {     // eight channels -> one word, channel c at bits 4c .. 4c + 2
@@ -96,7 +85,7 @@ __device__ __forceinline__ uint32_t ws_code_word(const u32x4 (&p)[CNT]) {     //
 #pragma unroll
     for (int e = 0; e < CNT; ++e) { x[e] = p[e].x; y[e] = p[e].y; z[e] = p[e].z; w[e] = p[e].w; }
     const uint32_t c0 = ws_code2(x), c1 = ws_code2(y), c2 = ws_code2(z), c3 = ws_code2(w);
-    return ((c0 | (c0 >> 12)) & 0xffu) | (((c1 | (c1 >> 12)) & 0xffu) << 8) | (((c2 | (c2 >> 12)) & 0xffu) << 16) | ((c3 | (c3 >> 12)) << 24);
+    return pool_code2_merge(c0, c1, c2, c3);
 }
 
 // geometry of an instance — mirrored by tools/ws_plane_model.py (tests/test_ws_plane_model.py replays the index algebra on the CPU)

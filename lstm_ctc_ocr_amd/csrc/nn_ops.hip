@@ -4,6 +4,7 @@
 // coalesced along the channel axis of the reference layout [N, W, H, C].
 #include "common.h"
 #include <stdlib.h>
+#include <algorithm>
 
 __device__ __forceinline__ void unpack8(u32x4 p, float* f) {
     f[0] = bf_lo(p.x); f[1] = bf_hi(p.x); f[2] = bf_lo(p.y); f[3] = bf_hi(p.y);
@@ -131,28 +132,8 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const float* __restric
 // pooled gradient to the first maximum (TF scan order: W outer, H inner) and accumulates dW / db in registers.
 //   reference: LSTM_train.py:24-25 (conv_single 3x3 c_i=1 -> max_pool 2,2), network.py:160-191, 343-350
 // ============================================================================================
-// 4x4 input patch around the 2x2 output window (rows w0-1..w0+2, cols h0-1..h0+2), zero outside the image
-__device__ __forceinline__ void conv1_patch(const float* __restrict__ xn, int W, int H, int w0, int h0, float (&patch)[4][4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ww = w0 - 1 + i, hh = h0 - 1 + j;
-            patch[i][j] = ((unsigned)ww < (unsigned)W && (unsigned)hh < (unsigned)H) ? xn[(long)ww * H + hh] : 0.f;
-        }
-}
-// arg-max of the 2x2 window on the bf16-ROUNDED outputs (what the forward stores and an unfused max-pool backward would compare: ties resolve
-// to the first element in TF scan order) and the ReLU bit of the winner: code = best | (winner > 0) << 2
-__device__ __forceinline__ int conv1_pool_code(float o0, float o1, float o2, float o3) {
-    const float r[4] = {bf_lo(pack_bf2(o0, 0.f)), bf_lo(pack_bf2(o1, 0.f)), bf_lo(pack_bf2(o2, 0.f)), bf_lo(pack_bf2(o3, 0.f))};
-    int best = 0; float bvv = r[0];
-#pragma unroll
-    for (int e = 1; e < 4; ++e) if (r[e] > bvv) { bvv = r[e]; best = e; }
-    return best | ((bvv > 0.f) ? 4 : 0);
-}
-__device__ __forceinline__ void conv1_window(const float* __restrict__ xn, int W, int H, int w0, int h0,
-                                             const float (&wr)[9][8], const float (&br)[8], float (&o)[4][8], float (&patch)[4][4]) {
-    conv1_patch(xn, W, H, w0, h0, patch);
+// the 2x2 window's 4 x 8 outputs from its 4 x 4 patch: nine fused multiply-adds in tap order, + bias, ReLU
+__device__ __forceinline__ void conv1_window_fma(const float (&patch)[4][4], const float (&wr)[9][8], const float (&br)[8], float (&o)[4][8]) {
     // channel PAIRS per instruction (v_pk_fma_f32: two fp32 FMAs per lane at the rate of one — the kernel is VALU-bound): the same fused
     // multiply-adds in the same order per channel, hence bit-identical results (round 4)
     typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -176,6 +157,33 @@ __device__ __forceinline__ void conv1_window(const float* __restrict__ xn, int W
         }
     }
 }
+
+#ifdef OCR_EXPERIMENTS   // the first generation (OCR_CONV1_GEN=1): every lane loads its own patch from HBM; kept to measure the tile kernels below against
+// 4x4 input patch around the 2x2 output window (rows w0-1..w0+2, cols h0-1..h0+2), zero outside the image
+__device__ __forceinline__ void conv1_patch(const float* __restrict__ xn, int W, int H, int w0, int h0, float (&patch)[4][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int ww = w0 - 1 + i, hh = h0 - 1 + j;
+            patch[i][j] = ((unsigned)ww < (unsigned)W && (unsigned)hh < (unsigned)H) ? xn[(long)ww * H + hh] : 0.f;
+        }
+}
+// arg-max of the 2x2 window on the bf16-ROUNDED outputs (what the forward stores and an unfused max-pool backward would compare: ties resolve
+// to the first element in TF scan order) and the ReLU bit of the winner: code = best | (winner > 0) << 2
+__device__ __forceinline__ int conv1_pool_code(float o0, float o1, float o2, float o3) {
+    const float r[4] = {bf_lo(pack_bf2(o0, 0.f)), bf_lo(pack_bf2(o1, 0.f)), bf_lo(pack_bf2(o2, 0.f)), bf_lo(pack_bf2(o3, 0.f))};
+    int best = 0; float bvv = r[0];
+#pragma unroll
+    for (int e = 1; e < 4; ++e) if (r[e] > bvv) { bvv = r[e]; best = e; }
+    return best | ((bvv > 0.f) ? 4 : 0);
+}
+__device__ __forceinline__ void conv1_window(const float* __restrict__ xn, int W, int H, int w0, int h0,
+                                             const float (&wr)[9][8], const float (&br)[8], float (&o)[4][8], float (&patch)[4][4]) {
+    conv1_patch(xn, W, H, w0, h0, patch);
+    conv1_window_fma(patch, wr, br, o);
+}
+#endif
 
 #ifdef OCR_EXPERIMENTS   // measured and rejected: compiled, reachable (OCR_CONV1_V2=1) and tested only in the experiments flavour
 // Second generation of the two fused kernels (round 2; behind OCR_CONV1_V2=1 — measured slightly SLOWER than the first, see conv1_v1()).  The ISA of the first showed, per
@@ -358,6 +366,7 @@ void conv1_pool_bwd2_kernel(const float* __restrict__ x, const float* __restrict
 }
 #endif   // OCR_EXPERIMENTS (second-generation conv1 + pool kernels)
 
+#ifdef OCR_EXPERIMENTS   // first generation, continued: the grid-stride forward and the private-patch backward
 template <bool CODES>
 __device__ __forceinline__ void conv1_pool_fwd_body(const float* __restrict__ x, const float* __restrict__ w,
                                                     const float* __restrict__ bias, bf16_t* __restrict__ p,
@@ -498,6 +507,232 @@ __global__ __launch_bounds__(256) void conv1_pool_bwd_kernel(const float* __rest
         else atomicAdd(db + c, v);
     }
 }
+#endif   // OCR_EXPERIMENTS (first-generation conv1 + pool kernels)
+
+// --------------------------------------------------------------------------------------------
+// The shipped generation: a block owns a run of consecutive pooled pixels [p0, p1) and stages the input rows they touch in LDS once.
+// In memory x is rows of H floats, image n's row w at global row R = n * W + w; pooled column q = n * Wo + wo covers global rows 2q, 2q + 1.  A
+// run spans columns q0 .. q1, i.e. rows 2 q0 - 1 .. 2 q1 + 2, which are CONTIGUOUS in x (images follow each other): one coalesced pass loads
+// them, zero where the row lies before the first or behind the last image.  Tile row r = global row 2 q0 - 1 + r, stride RS = H + 2 words: word 0
+// and word H + 1 of a row are the zero padding left and right of the image.  Pixel (column q0 + qi, ho) takes patch[i][j] from
+// tile[(2 qi + i) * RS + 2 ho + j]: no bounds checks.  What a tile cannot express is the halo row of a column at an image's edge — it holds the
+// neighbouring image's row, real data for that image's own columns: the first patch row reads as zero where wo == 0, the last where wo == Wo - 1.
+// Banks: the lanes of one pixel (its channel groups) read one address (broadcast), neighbouring pixels are 2 words apart, a wave covers 8
+// pixels = 16 consecutive words (or, where the run wraps into the next column, words 2 RS = 2 H + 4 further on: distinct banks for H % 16 == 0).
+// Divisions: p0 / Ho and q0 % Wo once per block in 32 bits; per pixel v / d = umulhi(v, ceil(2^32 / d)), exact for v * d < 2^32 (the host checks;
+// reciprocal 0 stands for d == 1).
+struct Conv1Geo { int RS, Ho, Wo; unsigned ho0, wo0, rHo, rWo; };
+__device__ __forceinline__ unsigned conv1_div(unsigned v, unsigned r) { return r ? __umulhi(v, r) : v; }
+__device__ __forceinline__ Conv1Geo conv1_tile_stage(const float* __restrict__ x, int Nb, int W, int H, unsigned p0, unsigned p1, unsigned rH,
+                                                     unsigned rHo, unsigned rWo, float* __restrict__ tile) {
+    Conv1Geo g;
+    g.RS = H + 2; g.Ho = H >> 1; g.Wo = W >> 1; g.rHo = rHo; g.rWo = rWo;
+    const unsigned q0 = p0 / (unsigned)g.Ho, q1 = (p1 - 1) / (unsigned)g.Ho;
+    g.ho0 = p0 - q0 * (unsigned)g.Ho; g.wo0 = q0 % (unsigned)g.Wo;
+    const int rows = 2 * (int)(q1 - q0 + 1) + 2;
+    const long first = (2 * (long)q0 - 1) * H, total = (long)Nb * W * H;       // the tile's first word in x (row -1: before the first image)
+    for (unsigned i = threadIdx.x; i < (unsigned)(rows * H); i += 256) {
+        const unsigned r = __umulhi(i, rH), h = i - r * (unsigned)H;
+        const long e = first + i;
+        tile[r * g.RS + 1 + h] = (e >= 0 && e < total) ? x[e] : 0.f;
+    }
+    for (int r = threadIdx.x; r < rows; r += 256) { tile[r * g.RS] = 0.f; tile[r * g.RS + H + 1] = 0.f; }
+    __syncthreads();
+    return g;
+}
+// the run's i-th pixel: where its patch starts in the tile, and whether its first / last patch row lies outside its image
+struct Conv1Pix { const float* base; bool top, bottom; };
+__device__ __forceinline__ Conv1Pix conv1_tile_pixel(const float* __restrict__ tile, const Conv1Geo& g, unsigned i) {
+    const unsigned v = g.ho0 + i, qi = conv1_div(v, g.rHo), ho = v - qi * (unsigned)g.Ho;
+    const unsigned c = g.wo0 + qi, wo = c - conv1_div(c, g.rWo) * (unsigned)g.Wo;
+    Conv1Pix px = {tile + (2 * qi) * g.RS + 2 * ho, wo == 0, wo == (unsigned)g.Wo - 1};
+    return px;
+}
+__device__ __forceinline__ void conv1_tile_patch(const Conv1Pix& px, int RS, float (&patch)[4][4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) patch[a][b] = px.base[a * RS + b];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { patch[0][b] = px.top ? 0.f : patch[0][b]; patch[3][b] = px.bottom ? 0.f : patch[3][b]; }
+}
+// the window's outputs -> its pooled bf16 values (as 4 packed pairs) and routing codes.  Post-ReLU values are >= +0 (an accumulator that starts
+// at +0 never becomes -0, so neither does accumulator + bias), hence pool_code2_u16's integer order is the float order: the same first maximum on
+// the rounded values, the same ReLU bit, and max-then-round == round-then-max, as conv1_pool_code / the first generation's float max give.
+__device__ __forceinline__ uint32_t conv1_pool_pack(const float (&o)[4][8], u32x4& pk) {
+    uint32_t m[4], cd[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        uint32_t pe[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            pe[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){o[e][2 * q], o[e][2 * q + 1]}, bf16x2_t));
+        }
+        cd[q] = pool_code2_u16(pe, m[q]);
+    }
+    pk = (u32x4){m[0], m[1], m[2], m[3]};
+    return pool_code2_merge(cd[0], cd[1], cd[2], cd[3]);
+}
+
+template <bool CODES>
+__global__ __launch_bounds__(256) void conv1_pool_fwd_tile_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                                  bf16_t* __restrict__ p, int Nb, int W, int H, int Cout, int pix_per_block, unsigned rH,
+                                                                  unsigned rHo, unsigned rWo, f32x4* __restrict__ zero, long zero_n4,
+                                                                  uint32_t* __restrict__ codes, u32x4* __restrict__ ones, long ones_n4) {
+    extern __shared__ float conv1_tile[];
+    // the step's flat gradient buffer is cleared by the FIRST kernel of the forward pass (round 4: it was a fill launch of its own): the
+    // stores go out here and drain beside the VALU-bound work below.  Likewise `ones`: the hand-off blocks of the step's persistent LSTM
+    // launches, set to the all-ones pattern they start from (ocr_lstm_*_seq2 with OCR_LSTM_PREPARED: two fill launches less).
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < zero_n4; i += (long)gridDim.x * 256) zero[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < ones_n4; i += (long)gridDim.x * 256) ones[i] = (u32x4){~0u, ~0u, ~0u, ~0u};
+    const unsigned npix = (unsigned)Nb * (W >> 1) * (H >> 1);                       // < 2^31 (checked by the host)
+    const unsigned p0 = blockIdx.x * (unsigned)pix_per_block, p1 = min(npix, p0 + (unsigned)pix_per_block);
+    if (p0 >= npix) return;                                                         // (an empty batch still gets its fills)
+    const int groups = Cout >> 3, gq = threadIdx.x % groups, plane = threadIdx.x / groups, planes = 256 / groups;
+    float wr[9][8], br[8];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) wr[t][c] = w[t * Cout + gq * 8 + c];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) br[c] = bias[gq * 8 + c];
+    const Conv1Geo geo = conv1_tile_stage(x, Nb, W, H, p0, p1, rH, rHo, rWo, conv1_tile);
+    for (unsigned i = plane; i < p1 - p0; i += planes) {
+        float o[4][8], patch[4][4];
+        conv1_tile_patch(conv1_tile_pixel(conv1_tile, geo, i), geo.RS, patch);
+        conv1_window_fma(patch, wr, br, o);
+        u32x4 pk;
+        const uint32_t word = conv1_pool_pack(o, pk);
+        const long op = (long)p0 + i;
+        *(u32x4*)(p + op * Cout + gq * 8) = pk;
+        // training: the pool's routing and the ReLU bit per output, 4 bits each — the backward pass need not recompute the window
+        if constexpr (CODES) codes[op * groups + gq] = word;
+    }
+}
+
+// The reduction every conv1 + pool backward ends with: lane bits 8, 16, 32 by shuffles, the four waves through LDS, then the block's 640 sums
+// to its slab row or, without a slab, to dw / db by atomics.
+__device__ __forceinline__ void conv1_bwd_reduce(float (&acc)[10][8], float* __restrict__ dw, float* __restrict__ db, float* __restrict__ slab) {
+    __shared__ float red[4][10][64];
+#pragma unroll
+    for (int t = 0; t < 10; ++t)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            float v = acc[t][c];
+            v += __shfl_xor(v, 8, 64);
+            v += __shfl_xor(v, 16, 64);
+            v += __shfl_xor(v, 32, 64);
+            acc[t][c] = v;
+        }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane < 8) {
+#pragma unroll
+        for (int t = 0; t < 10; ++t)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) red[wave][t][lane * 8 + c] = acc[t][c];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 10 * 64; i += 256) {
+        int t = i / 64, c = i % 64;
+        float v = red[0][t][c] + red[1][t][c] + red[2][t][c] + red[3][t][c];
+        // slab form (round 4): this block's 640 partial sums go to its own row, the merged slab reduction that follows anyway adds the rows
+        // in a fixed order — 512 blocks x 640 same-address atomics were ~10 us of the kernel's 33 (it got SLOWER with more, smaller blocks:
+        // profiles/r04k), and the conv1 gradient was the last one that was not bit-reproducible
+        if (slab != nullptr) slab[(long)blockIdx.x * 640 + i] = v;
+        else if (t < 9) atomicAdd(dw + t * 64 + c, v);
+        else atomicAdd(db + c, v);
+    }
+}
+
+// Backward over the same tile.  Cout == 64: 8 channel groups x 32 pixel lanes, pixel lane pl takes the run's pixels pl, pl + 32, ... in order.
+// Routing without a lookup (LOOKUP == false, shipped): the gradient of a pooled output goes to window element `best`, i.e. tap t multiplies
+// patch[(best >> 1) + t / 3][(best & 1) + t % 3].  Instead of addressing the patch per channel, g_e = (best == e) ? gv : 0 for the four elements
+// and ALL 4 x 9 fused multiply-adds are issued per channel pair on the register-held patch: fma(p, 0, acc) == acc for finite p (acc is never
+// -0), so each accumulator sees the one effective fma per pixel the first generation made, bit for bit — 144 v_pk_fma_f32 and no LDS traffic
+// beyond the 16 broadcast reads of the patch, against 72 data-dependent LDS reads + 36 v_pk_fma_f32 (LOOKUP == true, experiments flavour,
+// OCR_CONV1_LOOKUP=1: the taps straight from the shared tile — 19.0 us against 17.3 at 64 x 256 x 32, 24.9 against 22.1 at 64 x 320 x 32,
+// profiles/r12_conv1_kernels.log).
+template <bool CODES /* routing + ReLU bits from the forward pass: no window recomputation */, bool LOOKUP>
+__global__ __launch_bounds__(256) void conv1_pool_bwd_tile_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                                  const bf16_t* __restrict__ dp, float* __restrict__ dw, float* __restrict__ db, int Nb,
+                                                                  int W, int H, int pix_per_block, unsigned rH, unsigned rHo, unsigned rWo,
+                                                                  const uint32_t* __restrict__ codes, float* __restrict__ slab) {
+    extern __shared__ float conv1_tile[];
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const int gq = threadIdx.x & 7, pl = threadIdx.x >> 3;
+    float wr[CODES ? 1 : 9][8], br[8];
+    if (!CODES) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) wr[CODES ? 0 : t][c] = w[t * 64 + gq * 8 + c];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) br[c] = bias[gq * 8 + c];
+    }
+    const unsigned npix = (unsigned)Nb * (W >> 1) * (H >> 1);                       // < 2^31 (checked by the host); the grid is ceil(npix / ppb) >= 1 blocks
+    const unsigned p0 = blockIdx.x * (unsigned)pix_per_block, p1 = min(npix, p0 + (unsigned)pix_per_block);
+    f32x2 acc2[10][4];
+#pragma unroll
+    for (int t = 0; t < 10; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc2[t][q] = (f32x2){0.f, 0.f};
+    const Conv1Geo geo = conv1_tile_stage(x, Nb, W, H, p0, p1, rH, rHo, rWo, conv1_tile);
+    for (unsigned i = pl; i < p1 - p0; i += 32) {
+        const long op = (long)p0 + i;
+        float patch[4][4];
+        uint32_t word = 0;
+        const Conv1Pix px = conv1_tile_pixel(conv1_tile, geo, i);
+        conv1_tile_patch(px, geo.RS, patch);
+        if constexpr (CODES) {
+            word = codes[op * 8 + gq];
+        } else {                        // the forward pass's arithmetic on the same values: the same codes
+            float o[4][8];
+            u32x4 pk;
+            conv1_window_fma(patch, wr, br, o);
+            word = conv1_pool_pack(o, pk);
+        }
+        float g[8];
+        unpack8(*(const u32x4*)(dp + op * 64 + gq * 8), g);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c0 = (int)((word >> (8 * q)) & 7u), c1 = (int)((word >> (8 * q + 4)) & 7u);
+            const f32x2 gv = {(c0 & 4) ? g[2 * q] : 0.f, (c1 & 4) ? g[2 * q + 1] : 0.f};        // ReLU mask of the winning element
+            acc2[9][q] += gv;
+            if constexpr (LOOKUP) {
+                const int a0 = c0 >> 1 & 1, a1 = c1 >> 1 & 1;
+                const float* t0 = px.base + a0 * geo.RS + (c0 & 1);
+                const float* t1 = px.base + a1 * geo.RS + (c1 & 1);
+                // patch row a + t / 3: row 0 (a == 0, first tap row) and row 3 (a == 1, last tap row) read as zero at an image's edge
+                const bool zt0 = px.top && !a0, zb0 = px.bottom && a0, zt1 = px.top && !a1, zb1 = px.bottom && a1;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    f32x2 xv = {t0[(t / 3) * geo.RS + t % 3], t1[(t / 3) * geo.RS + t % 3]};
+                    if (t / 3 == 0) xv = (f32x2){zt0 ? 0.f : xv.x, zt1 ? 0.f : xv.y};
+                    if (t / 3 == 2) xv = (f32x2){zb0 ? 0.f : xv.x, zb1 ? 0.f : xv.y};
+                    acc2[t][q] = __builtin_elementwise_fma(xv, gv, acc2[t][q]);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const f32x2 ge = {(c0 & 3) == e ? gv.x : 0.f, (c1 & 3) == e ? gv.y : 0.f};
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) {
+                        const float pv = patch[(e >> 1) + t / 3][(e & 1) + t % 3];
+                        acc2[t][q] = __builtin_elementwise_fma((f32x2){pv, pv}, ge, acc2[t][q]);
+                    }
+                }
+            }
+        }
+    }
+    float acc[10][8];
+#pragma unroll
+    for (int t = 0; t < 10; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { acc[t][2 * q] = acc2[t][q].x; acc[t][2 * q + 1] = acc2[t][q].y; }
+    conv1_bwd_reduce(acc, dw, db, slab);
+}
+
 
 // ============================================================================================
 // max-pool (VALID, window == stride, kw over axis W in {1,2}, kh over axis H in {1,2})
@@ -1434,12 +1669,17 @@ __global__ __launch_bounds__(256) void eltwise_bf16_kernel(int op, const bf16_t*
 // (145 registers = 3 waves per SIMD instead of 4), backward 40 us against 38.6 — the first generation's 64-bit divisions and branchy
 // loads are hidden by its occupancy.  OCR_COL2IM_V1=1: the scalar col2im (13.3 us against 5.9 for the 16-byte one).
 static bool nn_knob(const char* name, int slot) {
-    static int v[2] = {-1, -1};
+    static int v[4] = {-1, -1, -1, -1};
     if (v[slot] < 0) { const char* e = ocr_tune_env(name); v[slot] = (e && atoi(e) != 0) ? 1 : 0; }
     return v[slot] == 1;
 }
 #ifdef OCR_EXPERIMENTS
 static bool conv1_v1() { return !nn_knob("OCR_CONV1_V2", 0); }
+// OCR_CONV1_GEN=1: the first generation of the fused conv1 + pool kernels (per-lane patch loads from HBM, 64-bit index arithmetic, float-compare
+// codes, a private LDS patch per thread in the backward) in place of the tile kernels — what profiles/r12_conv1_* measure the latter against.
+// OCR_CONV1_LOOKUP=1: the tile backward with its taps read from the shared tile at data-dependent offsets instead of the select-and-multiply form.
+static bool conv1_gen1() { return nn_knob("OCR_CONV1_GEN", 2); }
+static bool conv1_lookup() { return nn_knob("OCR_CONV1_LOOKUP", 3); }
 #endif
 static bool col2im_v1() { return nn_knob("OCR_COL2IM_V1", 1); }      // product build: always false (ocr_tune_env); the scalar kernel is also the
                                                                      // fallback for HC % 8 != 0 / unaligned buffers, which is how the tests reach it
@@ -1475,6 +1715,30 @@ extern "C" int ocr_eltwise_bf16(int op, const void* a, const void* b, void* out,
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
+// Launch geometry of the tile kernels (conv1_tile_stage): ceil(npix / ppb) blocks (one at least: the forward's fills), the reciprocals of
+// conv1_div, and the dynamic LDS of the largest tile a run of ppb pooled pixels can need — it spans at most 2 + (ppb - 1) / Ho pooled columns,
+// two input rows each and a halo row either side, H + 2 words a row (4.9 KB at H = 32 and 256 pixels; 33 KB at H = 2 and 1024).  Refused: 2^31
+// pooled pixels or more, and shapes whose index products leave 32 bits or whose tile leaves the 160 KB of a CU (H > ~6800: six rows).
+struct Conv1Launch { bool ok; int blocks, ppb, lds; unsigned rH, rHo, rWo; };
+static unsigned conv1_recip(long d) { return d > 1 ? (unsigned)((0x100000000ull + (unsigned long)d - 1) / (unsigned long)d) : 0u; }
+static Conv1Launch conv1_launch(int Nb, int W, int H, int ppb) {
+    Conv1Launch L = {};
+    if (Nb < 0 || W < 2 || H < 2) return L;
+    const long Wo = W / 2, Ho = H / 2, npix = (long)Nb * Wo * Ho;
+    const long cols = std::min<long>(2 + (ppb - 1) / Ho, std::max<long>((long)Nb * Wo, 1)), words = (2 * cols + 2) * (H + 2);
+    if (npix >= 0x7fffffffL || words * 4 > 160 * 1024) return L;
+    if ((Ho + ppb) * Ho >= 0x100000000L || (Wo + cols) * Wo >= 0x100000000L || words * H >= 0x100000000L) return L;
+    L.ok = true; L.ppb = ppb; L.blocks = std::max(1, ceil_div(npix, ppb)); L.lds = (int)words * 4;
+    L.rH = conv1_recip(H); L.rHo = conv1_recip(Ho); L.rWo = conv1_recip(Wo);
+    return L;
+}
+// pooled pixels per block of the forward: 128 = 1024 blocks at the headline shape; 64 and 256 measured the same within 1 us (a tuning knob:
+// experiments flavour, profiles/r12_conv1_kernels.log)
+static int conv1_fwd_ppb() {
+    static int v = -1;
+    if (v < 0) { const char* e = ocr_tune_env("OCR_CONV1_FWD_PPB"); v = e ? atoi(e) : 128; if (v < 32 || v > 1024 || (v & 31)) v = 128; }
+    return v;
+}
 static int conv1_pool_fwd_impl(const float* x, const float* w, const float* bias, void* p, int Nb, int W, int H, int Cout,
                                float* zero, long zero_n, void* codes, void* ones, long ones_n, void* stream) {
     if (!x || !w || !bias || !p || (Cout & 7) || Cout > 1024 || 256 % (Cout >> 3) || (W & 1) || (H & 1)) return OCR_ERR_INVALID;
@@ -1482,16 +1746,26 @@ static int conv1_pool_fwd_impl(const float* x, const float* w, const float* bias
     if (ones_n < 0 || (ones_n & 3) || (ones_n && (!ones || ((size_t)ones & 15)))) return OCR_ERR_INVALID;
     if (codes && (Cout != 64 || ((size_t)codes & 3))) return OCR_ERR_INVALID;            // the routing codes exist for the 64-filter layer the backward kernel handles
     long total = (long)Nb * (W / 2) * (H / 2) * (Cout >> 3);
+    const Conv1Launch L = conv1_launch(Nb, W, H, conv1_fwd_ppb());
+    if (!L.ok) return OCR_ERR_INVALID;
 #ifdef OCR_EXPERIMENTS
     if (!zero_n && !ones_n && !codes && !conv1_v1() && (long)Nb * (W / 2) * (H / 2) < 0x7fffffffL && (long)Nb * W * H < 0x7fffffffL && (long)W * H < 0x7fffffffL)
         conv1_pool_fwd2_kernel<<<grid_for(total, 2048), 256, 0, (hipStream_t)stream>>>(x, w, bias, (bf16_t*)p, Nb, W, H, Cout);
-    else
-#endif
-    {
+    else if (conv1_gen1()) {
         if (codes) conv1_pool_fwd_kernel<true><<<grid_for(total, 2048), 256, 0, (hipStream_t)stream>>>(x, w, bias, (bf16_t*)p, Nb, W, H, Cout, (f32x4*)zero,
                                                                                                           zero_n / 4, (uint32_t*)codes, (u32x4*)ones, ones_n / 4);
         else conv1_pool_fwd_kernel<false><<<grid_for(total, 2048), 256, 0, (hipStream_t)stream>>>(x, w, bias, (bf16_t*)p, Nb, W, H, Cout, (f32x4*)zero,
                                                                                                  zero_n / 4, nullptr, (u32x4*)ones, ones_n / 4);
+    } else
+#endif
+    if (codes) {
+        if (ocr_allow_lds<conv1_pool_fwd_tile_kernel<true>>(L.lds) != hipSuccess) return OCR_ERR_EXEC;
+        conv1_pool_fwd_tile_kernel<true><<<L.blocks, 256, L.lds, (hipStream_t)stream>>>(x, w, bias, (bf16_t*)p, Nb, W, H, Cout, L.ppb, L.rH, L.rHo, L.rWo,
+                                                                                       (f32x4*)zero, zero_n / 4, (uint32_t*)codes, (u32x4*)ones, ones_n / 4);
+    } else {
+        if (ocr_allow_lds<conv1_pool_fwd_tile_kernel<false>>(L.lds) != hipSuccess) return OCR_ERR_EXEC;
+        conv1_pool_fwd_tile_kernel<false><<<L.blocks, 256, L.lds, (hipStream_t)stream>>>(x, w, bias, (bf16_t*)p, Nb, W, H, Cout, L.ppb, L.rH, L.rHo, L.rWo,
+                                                                                        (f32x4*)zero, zero_n / 4, nullptr, (u32x4*)ones, ones_n / 4);
     }
     OCR_CHECK_LAUNCH();
     return OCR_OK;
@@ -1516,23 +1790,33 @@ static int conv1_ppb() {
     if (v < 0) { const char* e = getenv("OCR_CONV1_PPB"); v = e ? atoi(e) : 256; if (v < 32 || v > 1024 || (v & 31)) v = 256; }
     return v;
 }
+#define CONV1_BWD_TILE(CODES, LOOKUP)                                                                                              \
+    do {                                                                                                                           \
+        if (ocr_allow_lds<conv1_pool_bwd_tile_kernel<CODES, LOOKUP>>(L.lds) != hipSuccess) return OCR_ERR_EXEC;                    \
+        conv1_pool_bwd_tile_kernel<CODES, LOOKUP><<<nb, 256, L.lds, (hipStream_t)stream>>>(x, w, bias, g, dw, db, Nb, W, H, ppb,    \
+                                                                                            L.rH, L.rHo, L.rWo, cd, slab);         \
+    } while (0)
 static int conv1_pool_bwd_impl(const float* x, const float* w, const float* bias, const void* dp, float* dw, float* db,
                                int Nb, int W, int H, int Cout, const void* codes, float* slab, void* stream) {
     if (!x || !w || !bias || !dp || (!slab && (!dw || !db)) || Cout != 64 || (W & 1) || (H & 1) || ((size_t)codes & 3)) return OCR_ERR_INVALID;
     long npix = (long)Nb * (W / 2) * (H / 2);
     int ppb = slab ? conv1_ppb() : 256;
+    const Conv1Launch L = conv1_launch(Nb, W, H, ppb);
+    if (!L.ok) return OCR_ERR_INVALID;
+    const bf16_t* g = (const bf16_t*)dp;
+    const uint32_t* cd = (const uint32_t*)codes;
+    const int nb = ceil_div(npix, ppb);
 #ifdef OCR_EXPERIMENTS
     if (!codes && !slab && !conv1_v1() && npix < 0x7fffffffL - 512 && (long)Nb * W * H < 0x7fffffffL)
-        conv1_pool_bwd2_kernel<<<ceil_div(npix, ppb), 256, 0, (hipStream_t)stream>>>(x, w, bias, (const bf16_t*)dp, dw, db, Nb, W, H,
-                                                                                     Cout, ppb);
-    else
+        conv1_pool_bwd2_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(x, w, bias, g, dw, db, Nb, W, H, Cout, ppb);
+    else if (conv1_gen1()) {
+        if (codes) conv1_pool_bwd_kernel<true><<<nb, 256, 0, (hipStream_t)stream>>>(x, w, bias, g, dw, db, Nb, W, H, Cout, ppb, cd, slab);
+        else conv1_pool_bwd_kernel<false><<<nb, 256, 0, (hipStream_t)stream>>>(x, w, bias, g, dw, db, Nb, W, H, Cout, ppb, nullptr, slab);
+    } else if (conv1_lookup()) {
+        if (codes) CONV1_BWD_TILE(true, true); else CONV1_BWD_TILE(false, true);
+    } else
 #endif
-    {
-        if (codes) conv1_pool_bwd_kernel<true><<<ceil_div(npix, ppb), 256, 0, (hipStream_t)stream>>>(x, w, bias, (const bf16_t*)dp, dw, db, Nb, W, H,
-                                                                                                   Cout, ppb, (const uint32_t*)codes, slab);
-        else conv1_pool_bwd_kernel<false><<<ceil_div(npix, ppb), 256, 0, (hipStream_t)stream>>>(x, w, bias, (const bf16_t*)dp, dw, db, Nb, W, H,
-                                                                                               Cout, ppb, nullptr, slab);
-    }
+    if (codes) CONV1_BWD_TILE(true, false); else CONV1_BWD_TILE(false, false);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
