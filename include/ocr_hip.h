@@ -49,6 +49,19 @@ int ocr_ctc_loss_train(const float* activations, void* grad_ntc_bf16, float scal
                        const int* label_lengths, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
                        int max_label_len, int blank_label, float* costs, void* stream);
 int ocr_set_ctc_engine(int fast);   /* 1 (default): 4-wave LDS-resident kernel where it fits; 0: one-wave general kernel */
+/* long labels, 1 <= max_label_len <= 255 (S = 2L+1 <= 511): one launch, one 16-wave workgroup per sample, 2 / 4 / 8 extended-label slots
+ * per lane.  Same semantics as ocr_ctc_loss; label offsets computed in-kernel.  Writes the f32 [T][N][C] gradient, the bf16 [N][T][C]
+ * gradient multiplied by `scale`, both, or neither (score only).  The [T][S] tables live in LDS when they fit and in `workspace`
+ * otherwise: ocr_ctc_long_placement = 0 not covered, 1 LDS, 2 workspace (arithmetic only); ocr_ctc_long_workspace_size gives 0 bytes for
+ * placement 1, and `workspace` may then be NULL.  ocr_ctc_long_supported = placement != 0 and the device grants the LDS. */
+int ocr_ctc_long_placement(int alphabet_size, int max_time, int max_label_len);
+int ocr_ctc_long_supported(int alphabet_size, int max_time, int max_label_len);
+int ocr_ctc_long_workspace_size(int alphabet_size, int max_label_len, int max_time, int minibatch, size_t* bytes);
+int ocr_ctc_loss_long(const float* activations, float* gradients /* f32 [T][N][C] or NULL */,
+                      void* grad_ntc_bf16 /* [N][T][C] or NULL */, float scale,
+                      const int* flat_labels, const int* label_lengths, const int* input_lengths,
+                      int alphabet_size, int minibatch, int max_time, int max_label_len, int blank_label,
+                      float* costs, void* workspace, size_t workspace_bytes, void* stream);
 /* best-path decode (argmax, collapse repeats, drop blank): the greedy counterpart of
  * tf.nn.ctc_beam_search_decoder + sparse_tensor_to_dense(default 0) at network.py:656-657 / test.py:30-31.
  * decoded: int32 [minibatch, max_time] padded with pad_value; decoded_lengths: int32 [minibatch]. */

@@ -11,6 +11,8 @@
  *   CTC_STATUS_EXECUTION_FAILED, loudly, instead of computing on the host);  options.stream is a hipStream_t;
  *   the call returns after the costs have arrived in host memory (warp-ctc synchronises its stream the same way).
  * Infeasible samples (label longer than the input allows) get cost 0 and a zero gradient, like warp-ctc.
+ * Labels of up to 255 characters: a batch whose longest label exceeds 127 runs the long-label form (ocr_ctc_loss_long); 256 and more
+ * return CTC_STATUS_INVALID_VALUE.
  * The training loop itself uses ocr_ctc_loss_train (include/ocr_hip.h), which keeps labels and costs in HBM and never syncs.
  */
 #ifndef WARPCTC_ABI_H

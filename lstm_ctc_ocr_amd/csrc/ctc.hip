@@ -574,3 +574,260 @@ extern "C" int ocr_ctc_greedy_decode(const float* activations, const int* input_
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Long labels (1 <= L <= 255, S = 2L+1 <= 511): the fast kernel's four phases with VT = 2, 4 or 8 extended-label slots per lane.
+//   phases 1, 2, 4  all 16 waves, frame-parallel, as in ctc_fast_kernel
+//   phase 3         wave 0 runs alpha while wave 1 runs beta.  Lane l owns the VT consecutive slots s = l * VT + v and keeps them in
+//                   registers; a step is VT independent lse3_flat updates, and only the two values that cross a lane boundary move
+//                   (two whole-wave DPP shifts).  No barrier and no LDS exchange on the chain; the next step's logy values are loaded
+//                   one step ahead, and alpha / beta are only ever stored by these waves.
+// Tables logy / alpha / beta are [T][SP], SP = 64 * VT, element (t, s) at t * SP + (s % VT) * 64 + s / VT: what a lane owns is SP / 64
+// words 64 apart, so every table access of the recursions and of phase 4 is one conflict-free LDS read or one coalesced 256-B line.
+// Slots s >= S hold logy = -inf, which keeps their alpha / beta at -inf without a test on the chain.
+// Placement (ctc_long_placement): the three tables live in LDS when they fit beside lse[T], the per-wave class accumulators and the
+// extended labels (TLDS); otherwise in the caller's workspace, 3 * T * SP floats per sample.  The workspace is written and read by ONE
+// workgroup, ordered by the __syncthreads() between the phases: its pointer is deliberately neither __restrict__ nor const.
+// ------------------------------------------------------------------------------------------------------------------
+// log(e^a + e^b + e^c) as straight-line code on the bare v_exp_f32 / v_log_f32: with every input -inf the maximum is replaced by 0, the
+// sum is 0 and v_log_f32 returns -inf, so no branch guards the (-inf) - (-inf) case and the VT updates of a step interleave; the sum
+// of a finite case lies in [1, 3], so the denormal scaling of __logf is not needed either
+__device__ __forceinline__ float lse3_flat(float a, float b, float c) {
+    const float m = fmaxf(fmaxf(a, b), c);
+    const float m0 = (m == NEG_INF) ? 0.f : m;
+    constexpr float LOG2E = 1.44269504088896341f, LN2 = 0.693147180559945309f;
+    const float sum = __builtin_amdgcn_exp2f((a - m0) * LOG2E) + __builtin_amdgcn_exp2f((b - m0) * LOG2E) + __builtin_amdgcn_exp2f((c - m0) * LOG2E);
+    return m0 + __builtin_amdgcn_logf(sum) * LN2;
+}
+
+template <int VT, bool TLDS>
+__global__ __launch_bounds__(64 * CTC_NW) void ctc_long_kernel(
+    const float* __restrict__ act, float* __restrict__ grad, const int* __restrict__ flat_labels,
+    const int* __restrict__ label_len, const int* __restrict__ input_len, int T, int N, int C, int blank,
+    float* __restrict__ costs, bf16_t* __restrict__ grad_ntc, float scale, float* ws) {
+    constexpr int SP = 64 * VT;
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    extern __shared__ __attribute__((aligned(16))) float lsm[];
+    float* lse = lsm;                          // [T]
+    float* acc = lse + T;                      // [CTC_NW][C]
+    int* lab = (int*)(acc + CTC_NW * C);       // [SP]
+    float* logy = TLDS ? (float*)(lab + SP) : ws + (size_t)n * 3 * T * SP;     // [T][SP] each
+    float* alpha = logy + (size_t)T * SP;
+    float* beta = alpha + (size_t)T * SP;
+    __shared__ float s_logp;
+    __shared__ int s_repeats, s_off;
+
+    const int L = label_len[n];
+    const int Tn = min(input_len[n], T);
+    const int S = 2 * L + 1;
+    const size_t tstride = (size_t)N * C;
+    const float* a_n = act + (size_t)n * C;
+    float* g_n = grad ? grad + (size_t)n * C : nullptr;
+    bf16_t* gb_n = grad_ntc ? grad_ntc + (size_t)n * T * C : nullptr;
+    const bool want_grad = g_n || gb_n;
+
+    if (tid == 0) { s_repeats = 0; s_off = 0; }
+    __syncthreads();
+    {                                      // exclusive prefix sum of the label lengths
+        int part = 0;
+        for (int i = tid; i < n; i += 64 * CTC_NW) part += label_len[i];
+        if (part) atomicAdd(&s_off, part);
+        __syncthreads();
+    }
+    const int* labels = flat_labels + s_off;
+    const bool fits = L >= 0 && S <= SP;   // a label longer than the declared capacity has no table: treated like an infeasible sample
+    int rep = 0;
+    for (int s = tid; s < SP; s += 64 * CTC_NW) {
+        const bool in = fits && s < S;
+        lab[s] = (in && (s & 1)) ? labels[s >> 1] : blank;
+        if (in && (s & 1) && s >= 3 && labels[s >> 1] == labels[(s >> 1) - 1]) rep++;
+    }
+    if (rep) atomicAdd(&s_repeats, rep);
+    __syncthreads();
+    const bool feasible = fits && (Tn > 0) && (L + s_repeats <= Tn);
+    if (want_grad) {    // frames this sample does not own (and everything when infeasible): zero gradient
+        const int t0 = feasible ? Tn : 0;
+        for (int t = t0 + wave; t < T; t += CTC_NW)
+            for (int k = lane; k < C; k += 64) {
+                if (g_n) g_n[t * tstride + k] = 0.f;
+                if (gb_n) gb_n[(size_t)t * C + k] = 0;
+            }
+    }
+    if (!feasible) { if (tid == 0) costs[n] = 0.f; return; }
+
+    // phase 1: softmax denominators
+    for (int t = wave; t < Tn; t += CTC_NW) {
+        const float* row = a_n + t * tstride;
+        float m = NEG_INF;
+        for (int k = lane; k < C; k += 64) m = fmaxf(m, row[k]);
+        m = wave_max(m);
+        float sum = 0.f;
+        for (int k = lane; k < C; k += 64) sum += expf(row[k] - m);
+        sum = wave_sum(sum);
+        if (lane == 0) lse[t] = m + logf(sum);
+    }
+    __syncthreads();
+    // phase 2: logy table, every slot of every owned frame (-inf beyond S)
+    for (int i = tid; i < Tn * SP; i += 64 * CTC_NW) {
+        const int t = i / SP, j = i & (SP - 1);
+        const int s = (j & 63) * VT + (j >> 6);
+        logy[i] = (s < S) ? a_n[t * tstride + lab[s]] - lse[t] : NEG_INF;
+    }
+    __syncthreads();
+    // phase 3
+    if (wave == 0) {
+        bool skip[VT];
+        float a[VT], ly[VT];
+#pragma unroll
+        for (int v = 0; v < VT; ++v) {
+            const int s = lane * VT + v;
+            skip[v] = s < S && s >= 2 && lab[s] != blank && lab[s] != lab[s - 2];
+            a[v] = (s < 2) ? logy[v * 64 + lane] : NEG_INF;
+            if (want_grad) alpha[v * 64 + lane] = a[v];
+            ly[v] = logy[(size_t)min(1, Tn - 1) * SP + v * 64 + lane];
+        }
+        for (int t = 1; t < Tn; ++t) {
+            float lyn[VT];
+            const float* nrow = logy + (size_t)min(t + 1, Tn - 1) * SP + lane;
+#pragma unroll
+            for (int v = 0; v < VT; ++v) lyn[v] = nrow[v * 64];
+            const float p1 = wave_shr1(a[VT - 1], NEG_INF), p2 = wave_shr1(a[VT - 2], NEG_INF);
+            float na[VT];
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                const float x1 = v >= 1 ? a[v >= 1 ? v - 1 : 0] : p1;
+                const float x2 = v >= 2 ? a[v >= 2 ? v - 2 : 0] : (v == 1 ? p1 : p2);
+                na[v] = lse3_flat(a[v], x1, skip[v] ? x2 : NEG_INF) + ly[v];
+            }
+            float* arow = alpha + (size_t)t * SP + lane;
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                a[v] = na[v]; ly[v] = lyn[v];
+                if (want_grad) arow[v * 64] = a[v];
+            }
+        }
+        float x1 = NEG_INF, x2 = NEG_INF;
+#pragma unroll
+        for (int v = 0; v < VT; ++v) {
+            if (v == ((S - 1) & (VT - 1))) x1 = a[v];
+            if (S >= 2 && v == ((S - 2) & (VT - 1))) x2 = a[v];
+        }
+        const float e1 = __shfl(x1, (S - 1) / VT, 64);
+        const float e2 = (S >= 2) ? __shfl(x2, (S - 2) / VT, 64) : NEG_INF;
+        if (lane == 0) { s_logp = lse2(e1, e2); costs[n] = -s_logp; }
+    } else if (wave == 1 && want_grad) {
+        bool skip[VT];
+        float b[VT], ly[VT];
+#pragma unroll
+        for (int v = 0; v < VT; ++v) {
+            const int s = lane * VT + v;
+            skip[v] = (s + 2 < S) && lab[s + 2] != blank && lab[s + 2] != lab[s];
+            b[v] = (s >= S - 2) ? logy[(size_t)(Tn - 1) * SP + v * 64 + lane] : NEG_INF;    // -inf for s >= S
+            beta[(size_t)(Tn - 1) * SP + v * 64 + lane] = b[v];
+            ly[v] = logy[(size_t)max(Tn - 2, 0) * SP + v * 64 + lane];
+        }
+        for (int t = Tn - 2; t >= 0; --t) {
+            float lyn[VT];
+            const float* nrow = logy + (size_t)max(t - 1, 0) * SP + lane;
+#pragma unroll
+            for (int v = 0; v < VT; ++v) lyn[v] = nrow[v * 64];
+            const float q1 = wave_shl1(b[0], NEG_INF), q2 = wave_shl1(b[1], NEG_INF);
+            float nb[VT];
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                const float x1 = v + 1 < VT ? b[v + 1 < VT ? v + 1 : 0] : q1;
+                const float x2 = v + 2 < VT ? b[v + 2 < VT ? v + 2 : 0] : (v + 2 == VT ? q1 : q2);
+                nb[v] = lse3_flat(b[v], x1, skip[v] ? x2 : NEG_INF) + ly[v];
+            }
+            float* brow = beta + (size_t)t * SP + lane;
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                b[v] = nb[v]; ly[v] = lyn[v];
+                brow[v * 64] = b[v];
+            }
+        }
+    }
+    __syncthreads();
+    if (!want_grad) return;
+    // phase 4: gradient rows
+    const float logp = s_logp;
+    float* wacc = acc + wave * C;
+    for (int t = wave; t < Tn; t += CTC_NW) {
+        for (int k = lane; k < C; k += 64) wacc[k] = 0.f;
+        const size_t base = (size_t)t * SP + lane;
+#pragma unroll
+        for (int v = 0; v < VT; ++v) {
+            const int s = lane * VT + v;
+            if (s < S) {
+                const float al = alpha[base + v * 64], be = beta[base + v * 64];
+                if (al != NEG_INF && be != NEG_INF) atomicAdd(&wacc[lab[s]], expf(al + be - logy[base + v * 64] - logp));
+            }
+        }
+        const float* row = a_n + t * tstride;
+        const float l = lse[t];
+        for (int k = lane; k < C; k += 64) {
+            const float v = expf(row[k] - l) - wacc[k];
+            if (g_n) g_n[t * tstride + k] = v;
+            if (gb_n) gb_n[(size_t)t * C + k] = f2bf(v * scale);
+        }
+    }
+}
+
+constexpr size_t CTC_LONG_LDS_MAX = 128 * 1024;
+constexpr int CTC_LONG_MAX_LABEL = 255;
+static inline int ctc_long_vt(int max_label_len) { const int s = smax_for(max_label_len); return s <= 128 ? 2 : s <= 256 ? 4 : 8; }
+// LDS without the tables: lse[T], acc[CTC_NW][C], lab[SP]
+static size_t ctc_long_lds_base(int C, int T, int SP) { return ((size_t)T + (size_t)CTC_NW * C + SP) * sizeof(float); }
+static size_t ctc_long_table_bytes(int T, int SP) { return (size_t)3 * T * SP * sizeof(float); }
+// 0: not covered; 1: tables in LDS; 2: tables in the workspace.  Arithmetic only.
+extern "C" int ocr_ctc_long_placement(int alphabet_size, int max_time, int max_label_len) {
+    if (alphabet_size <= 0 || max_time <= 0 || max_label_len <= 0 || max_label_len > CTC_LONG_MAX_LABEL) return 0;
+    const int SP = 64 * ctc_long_vt(max_label_len);
+    const size_t base = ctc_long_lds_base(alphabet_size, max_time, SP);
+    if (base > CTC_LONG_LDS_MAX) return 0;
+    return base + ctc_long_table_bytes(max_time, SP) <= CTC_LONG_LDS_MAX ? 1 : 2;
+}
+template <int VT, bool TLDS>
+static int ctc_long_launch(const float* act, float* grad, bf16_t* gb, float scale, const int* labels, const int* ll, const int* il, int C, int N,
+                           int T, int blank, float* costs, float* ws, size_t lds, hipStream_t stream, bool launch) {
+    if (ocr_allow_lds<ctc_long_kernel<VT, TLDS>>((int)CTC_LONG_LDS_MAX) != hipSuccess) return OCR_ERR_INVALID;
+    if (!launch) return OCR_OK;
+    ctc_long_kernel<VT, TLDS><<<N, 64 * CTC_NW, lds, stream>>>(act, grad, labels, ll, il, T, N, C, blank, costs, gb, scale, ws);
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}
+static int ctc_long_dispatch(const float* act, float* grad, bf16_t* gb, float scale, const int* labels, const int* ll, const int* il, int C, int N,
+                             int T, int max_label_len, int blank, float* costs, float* ws, hipStream_t stream, bool launch) {
+    const int place = ocr_ctc_long_placement(C, T, max_label_len);
+    if (!place) return OCR_ERR_INVALID;
+    const int VT = ctc_long_vt(max_label_len);
+    const size_t lds = ctc_long_lds_base(C, T, 64 * VT) + (place == 1 ? ctc_long_table_bytes(T, 64 * VT) : 0);
+#define CTC_LONG_CASE(V, B) return ctc_long_launch<V, B>(act, grad, gb, scale, labels, ll, il, C, N, T, blank, costs, ws, lds, stream, launch)
+    if (place == 1) { if (VT == 2) CTC_LONG_CASE(2, true); if (VT == 4) CTC_LONG_CASE(4, true); CTC_LONG_CASE(8, true); }
+    if (VT == 2) CTC_LONG_CASE(2, false);
+    if (VT == 4) CTC_LONG_CASE(4, false);
+    CTC_LONG_CASE(8, false);
+#undef CTC_LONG_CASE
+}
+extern "C" int ocr_ctc_long_supported(int alphabet_size, int max_time, int max_label_len) {
+    return ctc_long_dispatch(nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, alphabet_size, 1, max_time, max_label_len, 0, nullptr,
+                             nullptr, nullptr, false) == OCR_OK;
+}
+extern "C" int ocr_ctc_long_workspace_size(int alphabet_size, int max_label_len, int max_time, int minibatch, size_t* bytes) {
+    if (!bytes || minibatch <= 0) return OCR_ERR_INVALID;
+    const int place = ocr_ctc_long_placement(alphabet_size, max_time, max_label_len);
+    if (!place) return OCR_ERR_INVALID;
+    *bytes = place == 1 ? 0 : (((size_t)minibatch * ctc_long_table_bytes(max_time, 64 * ctc_long_vt(max_label_len)) + 255) & ~(size_t)255);
+    return OCR_OK;
+}
+extern "C" int ocr_ctc_loss_long(const float* activations, float* gradients, void* grad_ntc_bf16, float scale, const int* flat_labels,
+                                 const int* label_lengths, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
+                                 int max_label_len, int blank_label, float* costs, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!activations || !flat_labels || !label_lengths || !input_lengths || !costs) return OCR_ERR_INVALID;
+    if (alphabet_size <= 0 || minibatch <= 0 || max_time <= 0 || blank_label < 0 || blank_label >= alphabet_size) return OCR_ERR_INVALID;
+    size_t need = 0;
+    if (ocr_ctc_long_workspace_size(alphabet_size, max_label_len, max_time, minibatch, &need) != OCR_OK) return OCR_ERR_INVALID;
+    if (need && (!workspace || workspace_bytes < need)) return OCR_ERR_INVALID;
+    return ctc_long_dispatch(activations, gradients, (bf16_t*)grad_ntc_bf16, scale, flat_labels, label_lengths, input_lengths, alphabet_size,
+                             minibatch, max_time, max_label_len, blank_label, costs, (float*)workspace, (hipStream_t)stream_, true);
+}

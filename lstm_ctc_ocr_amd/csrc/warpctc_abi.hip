@@ -10,6 +10,10 @@ extern "C" int ocr_ctc_workspace_size(int max_label_len, int max_time, int minib
 extern "C" int ocr_ctc_loss(const float* activations, float* gradients, const int* flat_labels, const int* label_lengths,
                             const int* input_lengths, int alphabet_size, int minibatch, int max_time, int max_label_len,
                             int blank_label, float* costs, void* workspace, void* stream);
+extern "C" int ocr_ctc_long_workspace_size(int alphabet_size, int max_label_len, int max_time, int minibatch, size_t* bytes);
+extern "C" int ocr_ctc_loss_long(const float* activations, float* gradients, void* grad_ntc_bf16, float scale, const int* flat_labels,
+                                 const int* label_lengths, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
+                                 int max_label_len, int blank_label, float* costs, void* workspace, size_t workspace_bytes, void* stream);
 
 namespace {
 struct Extents { int max_t, max_l; long total_l; bool ok; };
@@ -23,6 +27,8 @@ Extents extents(const int* label_lengths, const int* input_lengths, int minibatc
     }
     return e;
 }
+// ocr_ctc_loss covers labels of at most 127 characters; a batch with a longer one goes to the long-label form (up to 255)
+constexpr int GENERAL_MAX_LABEL = 127;
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // staging area in front of the kernels' own workspace: labels, label lengths, input lengths, costs
 size_t staging_bytes(long total_l, int minibatch) {
@@ -49,7 +55,9 @@ extern "C" ctcStatus_t get_workspace_size(const int* const label_lengths, const 
     Extents e = extents(label_lengths, input_lengths, minibatch);
     if (!e.ok) return CTC_STATUS_INVALID_VALUE;
     size_t inner = 0;
-    if (ocr_ctc_workspace_size(e.max_l, e.max_t, minibatch, &inner) != OCR_OK) return CTC_STATUS_INVALID_VALUE;
+    if (e.max_l > GENERAL_MAX_LABEL) {
+        if (ocr_ctc_long_workspace_size(alphabet_size, e.max_l, e.max_t, minibatch, &inner) != OCR_OK) return CTC_STATUS_INVALID_VALUE;
+    } else if (ocr_ctc_workspace_size(e.max_l, e.max_t, minibatch, &inner) != OCR_OK) return CTC_STATUS_INVALID_VALUE;
     *size_bytes = staging_bytes(e.total_l, minibatch) + inner;
     return CTC_STATUS_SUCCESS;
 }
@@ -75,7 +83,14 @@ extern "C" ctcStatus_t compute_ctc_loss(const float* const activations, float* g
     if (hipMemcpyAsync(d_llen, label_lengths, (size_t)minibatch * 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
         hipMemcpyAsync(d_ilen, input_lengths, (size_t)minibatch * 4, hipMemcpyHostToDevice, stream) != hipSuccess)
         return CTC_STATUS_MEMOPS_FAILED;
-    int rc = ocr_ctc_loss(activations, gradients, d_labels, d_llen, d_ilen, alphabet_size, minibatch, e.max_t, e.max_l,
+    int rc;
+    if (e.max_l > GENERAL_MAX_LABEL) {
+        size_t inner = 0;
+        if (ocr_ctc_long_workspace_size(alphabet_size, e.max_l, e.max_t, minibatch, &inner) != OCR_OK) return CTC_STATUS_INVALID_VALUE;
+        rc = ocr_ctc_loss_long(activations, gradients, nullptr, 1.0f, d_labels, d_llen, d_ilen, alphabet_size, minibatch, e.max_t, e.max_l,
+                               options.blank_label, d_costs, ws, inner, stream);
+    } else
+        rc = ocr_ctc_loss(activations, gradients, d_labels, d_llen, d_ilen, alphabet_size, minibatch, e.max_t, e.max_l,
                           options.blank_label, d_costs, ws, stream);
     if (rc != OCR_OK) return (ctcStatus_t)rc;
     if (hipMemcpyAsync(costs, d_costs, (size_t)minibatch * 4, hipMemcpyDeviceToHost, stream) != hipSuccess)

@@ -1020,7 +1020,10 @@ class ShapePlan(object):
         self.T, _, self.C = self.oshape[eng.ops[-1].key]
         self.costs = torch.zeros(N, dtype=F32, device=dev)
         self.ctc_grad = torch.empty((self.T, N, self.C), dtype=F32, device=dev)
-        self.ctc_ws = torch.empty(ops.ctc_workspace_bytes(eng.max_label_len, self.T, N), dtype=torch.uint8, device=dev)
+        ws_bytes = ops.ctc_workspace_bytes(eng.max_label_len, self.T, N) if eng.max_label_len <= 127 else 1      # (the general kernel stops at 127)
+        if eng.ctc_path_of(self.C, self.T) == 'long':
+            ws_bytes = max(ws_bytes, ops.ctc_long_workspace_bytes(self.C, eng.max_label_len, self.T, N))
+        self.ctc_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         self.decoded = torch.zeros((N, self.T), dtype=I32, device=dev)
         self.decoded_len = torch.zeros(N, dtype=I32, device=dev)
         self.graph_fb = None
@@ -1032,8 +1035,10 @@ class Engine(object):
     """Owns parameters, optimiser state and per-shape plans for one Network on one GPU."""
 
     def __init__(self, net, device='cuda:0', seed=None, max_label_len=31, use_graphs=True, group=None,
-                 persistent_lstm=True, fuse_conv1_pool=True):
+                 persistent_lstm=True, fuse_conv1_pool=True, ctc_long=True):
         from .config import cfg
+        if max_label_len > self.CTC_MAX_LABEL_LEN:
+            raise ValueError('max_label_len = %d: the CTC loss covers labels of at most %d characters' % (max_label_len, self.CTC_MAX_LABEL_LEN))
         if not torch.cuda.is_available():
             raise NativeError('Engine needs a ROCm GPU: the hot path has no CPU implementation')
         self.cfg = cfg
@@ -1042,6 +1047,7 @@ class Engine(object):
         torch.cuda.set_device(self.device)
         self.num_features = cfg.NUM_FEATURES
         self.max_label_len = max_label_len
+        self.ctc_long = ctc_long          # False: the one-launch long-label kernel is never chosen (A/B switch)
         self.use_graphs = use_graphs
         self.persistent_lstm = persistent_lstm
         self.fuse_conv1_pool = fuse_conv1_pool
@@ -1406,9 +1412,13 @@ class Engine(object):
         logits = self.ops[-1].y(sp)
         # loss = mean over the GLOBAL batch -> d loss / d cost_n = 1 / (N * world)   (network.py:655)
         scale = ocr_dist.loss_scale(sp.N, self.world)
-        if ops.ctc_train_supported(sp.C, sp.T, self.max_label_len):
+        path = self.ctc_path_of(sp.C, sp.T)
+        if path == 'fast':
             ops.ctc_loss_train(logits, self.ops[-1].dy(sp), scale, sp.labels, sp.labels_len, sp.seq_len, self.max_label_len,
                                sp.costs, blank=0)
+        elif path == 'long':
+            ops.ctc_loss_long(logits, sp.labels, sp.labels_len, sp.seq_len, self.max_label_len, blank=0, want_grad=False,
+                              grad_ntc_bf16=self.ops[-1].dy(sp), scale=scale, workspace=sp.ctc_ws, costs=sp.costs)
         else:
             ops.ctc_loss(logits, sp.labels, sp.labels_len, sp.seq_len, self.max_label_len, blank=0, want_grad=True,
                          workspace=sp.ctc_ws, costs=sp.costs, grads=sp.ctc_grad)
@@ -1419,6 +1429,21 @@ class Engine(object):
         self._join_tn(sp)
         if flush:
             self._flush_w9(sp)
+
+    CTC_MAX_LABEL_LEN = 255
+
+    def ctc_path_of(self, C, T):
+        """Which CTC form a plan with T frames of C classes takes: 'fast' (ctc_fast_kernel's training form, S <= 64 with its tables in
+        LDS), 'long' (ctc_long_kernel, one launch, labels up to 255) or 'general' (scan + one-wave kernel + transpose)."""
+        if ops.ctc_train_supported(C, T, self.max_label_len):
+            return 'fast'
+        if self.ctc_long and ops.ctc_long_supported(C, T, self.max_label_len):
+            return 'long'
+        return 'general'
+
+    def ctc_path(self, N, W):
+        sp = self.plan(N, W)
+        return self.ctc_path_of(sp.C, sp.T)
 
     def _backward_early(self, sp):
         for op in reversed(self.ops[:self.split_op]):

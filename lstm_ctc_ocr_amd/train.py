@@ -179,7 +179,9 @@ def make_engine(network, use_graphs=True):
     if world > 1 and not torch.distributed.is_initialized():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         torch.distributed.init_process_group('nccl', device_id=torch.device('cuda', local_rank))
-    eng = Engine(network, device='cuda:%d' % local_rank, seed=cfg.RNG_SEED, use_graphs=use_graphs)
+    # label capacity of a plan's flat label vector: the engine's default, or the configured longest label where that is longer
+    eng = Engine(network, device='cuda:%d' % local_rank, seed=cfg.RNG_SEED, use_graphs=use_graphs,
+                 max_label_len=max(31, int(cfg.MAX_CHAR_LEN)))
     eng.rank = int(os.environ.get('RANK', '0'))
     return eng
 

@@ -6,7 +6,8 @@ device tensor of activations [T, N, C] (f32, unnormalised) and host label / leng
 with warp-ctc's exact prototype (ctcOptions by value, host labels, host costs) and returns the per-sample costs as a tensor
 that autograd can differentiate (d cost_n / d activations, scaled by the incoming gradient, like the registered TF gradient).
 The training engine does NOT use this entry point (it keeps labels and costs in HBM and never synchronises —
-ocr_ctc_loss_train); this one exists so that code written against warp-ctc finds the interface it expects.
+ocr_ctc_loss_train); this one exists so that code written against warp-ctc finds the interface it expects.  Labels of up to 255
+characters: the library sends a batch whose longest label exceeds 127 to its long-label kernel (ocr_ctc_loss_long).
 """
 import ctypes
 
