@@ -71,11 +71,24 @@ int ocr_ctc_greedy_decode(const float* activations, const int* input_lengths, in
 
 /* TF-semantics prefix beam search: tf.nn.ctc_beam_search_decoder(inputs, seq_len, beam_width=100, top_paths=1,
  * merge_repeated=True) as called at network.py:656 / test.py:30 — BLANK = alphabet_size-1, output dense + padded.
- * beam_width <= 128; neg_log_prob (may be NULL): f32 [minibatch].  Workspace from ocr_ctc_beam_workspace_size. */
+ * beam_width <= 128; neg_log_prob (may be NULL): f32 [minibatch].  Workspace from ocr_ctc_beam_workspace_size.
+ * Coverage: 1 <= beam_width <= 128 and 2 <= alphabet_size <= 16384, by one of two kernels with the same semantics, outputs, workspace
+ * layout and tie rule.  The table kernel keeps a score and a 16-bit child slot per (beam entry, class) in LDS and runs wherever
+ *   4*roundup4(C) + 4*(K + K*C) + 2*roundup2(K*C) + 6656 bytes (rounded up to 16) <= 160 KB   (C = alphabet_size, K = beam_width:
+ * C <= 259 at K = 100, C <= 202 at K = 128, C <= 15716 at K = 1; the query below answers for any shape).  Every other
+ * covered shape runs the wide kernel, which scores only the min(K + 1, C - 1) likeliest non-blank classes of each frame (exact: DESIGN
+ * section 6b) and needs 4*C + 4*K*(min(K + 1, C - 1) + 1) bytes plus the beam arrays.  Anything else is OCR_STATUS_INVALID from both
+ * entry points, and nothing is launched. */
 int ocr_ctc_beam_workspace_size(int alphabet_size, int minibatch, int max_time, int beam_width, size_t* bytes);
 int ocr_ctc_beam_decode(const float* activations, const int* input_lengths, int alphabet_size, int minibatch,
                         int max_time, int beam_width, int merge_repeated, int pad_value, int* decoded,
                         int* decoded_lengths, float* neg_log_prob, void* workspace, size_t workspace_bytes, void* stream);
+/* Which kernel ocr_ctc_beam_decode runs for a shape - a host-only query like ocr_conv3x3_kernel_choice (nothing is launched, works
+ * without a GPU): 0 refused, 1 table kernel, 2 wide kernel.  It honours ocr_set_beam_engine. */
+int ocr_ctc_beam_kernel_choice(int alphabet_size, int beam_width);
+/* A/B + test knob: 0 (default) = the table kernel wherever it fits, the wide kernel elsewhere; 2 = the wide kernel for every shape it
+ * covers (alphabet_size <= 16384).  OCR_STATUS_INVALID for any other value. */
+int ocr_set_beam_engine(int engine);
 
 /* ---- dense contractions (tf.nn.conv2d network.py:166, tf.matmul :126, LSTMCell matmul :104-107) ------------- */
 /* out[m][n] = sum_k P[m][k] * Q[n][k] (+bias[n]) ; bf16 operands, fp32 accumulate, K % 8 == 0, N % 4 == 0.

@@ -11,10 +11,23 @@
 // exact K-th-largest threshold by 32-step bisection on the order-preserving integer image of the floats -> ordered
 // compaction into the next beam -> trie bookkeeping (node pool in a caller-owned workspace).  This path runs at
 // validation / test time only; it is latency-, not throughput-critical.
+//
+// Two kernels share that body.  The TABLE kernel (WIDE = false) scores every (beam entry, class) pair and answers "is child (b, c)
+// already in the beam" from a 16-bit [K][C] table: about 6*K*C bytes of LDS, which at K = 100 ends at 259 classes.  The WIDE kernel
+// (WIDE = true) has no K*C term.  Per frame it first selects S, the M = min(K + 1, C - 1) non-blank classes with the largest lp (ties
+// at the boundary to the lowest class index), and scores only the pairs (b, S[j]).  That loses nothing: a new child b + c scores
+// lp[c] + tot[b] (or lp[c] + pb[b] <= that when c == last[b]); for c outside S at least K of the entries b + c', c' in S, c' != last[b],
+// score at least as much whether they are new or already in the beam, so b + c is not among the K best (ties aside, as above).  A child
+// that IS in the beam needs no candidate whatever its class: it gets its parent's mass in the leaf update (b).  S is kept in ascending
+// class order, so candidates keep the relative order of b*C + c and the tie rule of step (e) is the table kernel's.  The in-beam
+// question is answered without a table: each beam entry whose parent is in the beam looks its own label up in S (binary search) and
+// cancels that one candidate.  LDS: 4*C + 4*(K + K*M) + 4*M bytes plus the beam arrays, 136 KB at C = 16384, K = 128.
 #include "common.h"
 #include <math.h>
 
 #define BEAM_MAX 128
+#define BEAM_WIDE_MAX_C 16384        // the wide kernel's promise: 2 <= C <= 16384 for every K <= BEAM_MAX (node_label is a short)
+#define BEAM_LDS_LIMIT (160 * 1024)
 #define NEGINF (-INFINITY)
 
 __device__ __forceinline__ float blse(float a, float b) {
@@ -34,21 +47,24 @@ struct BeamArgs {
     int* node_parent; short* node_label; int* node_slot;     // per sample: T*K + 2 entries
 };
 
+template <bool WIDE>
 __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = a.C, K = a.K, blank = C - 1;
     const int Tn = min(a.input_len[n], a.T);
     const int pool = a.T * K + 2;
+    const int M = WIDE ? min(K + 1, C - 1) : C;           // candidate classes per beam entry (the table kernel scores all C)
     int* npar = a.node_parent + (size_t)n * pool;
     short* nlab = a.node_label + (size_t)n * pool;
     int* nslot = a.node_slot + (size_t)n * pool;
 
     // ---- LDS carve-up
     float* lp = (float*)smem_raw;                         // [C]
-    float* cand = lp + ((C + 3) & ~3);                    // [K + K*C]
-    short* table = (short*)(cand + K + K * C);            // [K][C] child slot of (parent slot, label) or -1
-    int* b_node = (int*)(table + ((K * C + 1) & ~1));     // beam arrays, two generations
+    float* cand = lp + ((C + 3) & ~3);                    // [K + K*M]
+    short* table = (short*)(cand + K + K * M);            // table kernel: [K][C] child slot of (parent slot, label) or -1
+    int* sel_cls = (int*)(cand + K + K * M);              // wide kernel: S[M], the frame's candidate classes in ascending order
+    int* b_node = WIDE ? sel_cls + M : (int*)(table + ((K * C + 1) & ~1));     // beam arrays, two generations
     int* b_last = b_node + 2 * BEAM_MAX;
     int* b_ps = b_last + 2 * BEAM_MAX;                    // slot of the parent entry if it is in the beam, else -1
     float* b_pb = (float*)(b_ps + 2 * BEAM_MAX);
@@ -66,7 +82,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         s_misc[0] = 1;        // beam size
         s_misc[1] = 1;        // nodes allocated
     }
-    for (int i = tid; i < K * C; i += 256) table[i] = -1;
+    if constexpr (!WIDE) for (int i = tid; i < K * C; i += 256) table[i] = -1;
     __syncthreads();
     int gen = 0;
     for (int t = 0; t < Tn; ++t) {
@@ -93,6 +109,50 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             for (int k = tid; k < C; k += 256) lp[k] = row[k] - lse;
         }
         __syncthreads();
+        // (a') wide kernel: S = the M non-blank classes with the largest lp, ascending.  M-th largest key by the bisection of step (d),
+        // then an ordered compaction that takes everything above it and the first M - (number above) ties in class order.
+        if constexpr (WIDE) {
+            if (M == blank) {
+                for (int j = tid; j < M; j += 256) sel_cls[j] = j;
+            } else {
+                unsigned lo = 0u, hi = 0xffffffffu;         // count(key >= 0) = C - 1 >= M
+                while (lo < hi) {
+                    const unsigned mid = lo + (unsigned)(((unsigned long long)hi - lo + 1ull) >> 1);
+                    int cnt = 0;
+                    for (int k = tid; k < blank; k += 256) cnt += (fkey(lp[k]) >= mid);
+                    cnt = (int)wave_sum((float)cnt);
+                    if (lane == 0) s_cnt[wave] = cnt;
+                    __syncthreads();
+                    cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+                    __syncthreads();
+                    if (cnt >= M) lo = mid; else hi = mid - 1u;
+                }
+                const unsigned thr = lo;
+                int above = 0;
+                for (int k = tid; k < blank; k += 256) above += (fkey(lp[k]) > thr);
+                above = (int)wave_sum((float)above);
+                if (lane == 0) s_cnt[wave] = above;
+                __syncthreads();
+                const int quota = M - (s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);      // ties to take, >= 1
+                if (wave == 0) {
+                    int filled = 0, ties = 0;
+                    for (int base = 0; base < blank; base += 64) {
+                        const int k = base + lane;
+                        const unsigned key = (k < blank) ? fkey(lp[k]) : 0u;
+                        const bool eq = (k < blank) && key == thr;
+                        const unsigned long long below = (1ull << lane) - 1ull;
+                        const unsigned long long eqmask = __ballot(eq);
+                        const bool take = (k < blank) && (key > thr || (eq && ties + __popcll(eqmask & below) < quota));
+                        const unsigned long long mask = __ballot(take);
+                        const int posn = filled + __popcll(mask & below);
+                        if (take && posn < M) sel_cls[posn] = k;
+                        filled += __popcll(mask);
+                        ties += __popcll(eqmask);
+                    }
+                }
+            }
+            __syncthreads();
+        }
         // (b) leaves stay in the beam with updated probabilities; cand[s] = new total
         float my_npb = NEGINF, my_npnb = NEGINF;
         if (tid < nb) {
@@ -108,19 +168,36 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             my_npb = tot[s] + lp[blank];
             cand[s] = blse(my_npb, my_npnb);
         }
-        // (c) children that are not in the beam: cand[nb + b*C + c]
-        for (int i = tid; i < nb * C; i += 256) {
-            const int b = i / C, c = i - b * C;
-            float v = NEGINF;
-            if (c != blank && table[b * C + c] < 0) {
-                const float prev = (c == last[b]) ? pb[b] : tot[b];
-                if (prev != NEGINF) v = prev + lp[c];
+        // (c) children that are not in the beam: cand[nb + b*C + c]  (wide: cand[nb + b*M + j] for class S[j])
+        if constexpr (!WIDE) {
+            for (int i = tid; i < nb * C; i += 256) {
+                const int b = i / C, c = i - b * C;
+                float v = NEGINF;
+                if (c != blank && table[b * C + c] < 0) {
+                    const float prev = (c == last[b]) ? pb[b] : tot[b];
+                    if (prev != NEGINF) v = prev + lp[c];
+                }
+                cand[nb + i] = v;
             }
-            cand[nb + i] = v;
+            __syncthreads();
+        } else {
+            for (int i = tid; i < nb * M; i += 256) {
+                const int b = i / M, c = sel_cls[i - b * M];
+                const float prev = (c == last[b]) ? pb[b] : tot[b];
+                cand[nb + i] = (prev != NEGINF) ? prev + lp[c] : NEGINF;
+            }
+            __syncthreads();
+            // a beam entry whose parent is in the beam cancels the candidate (parent, own label), if its label is in S
+            if (tid < nb && ps[tid] >= 0) {
+                const int c = last[tid];
+                int l = 0, r = M;                              // first j with S[j] >= c
+                while (l < r) { const int mid = (l + r) >> 1; if (sel_cls[mid] < c) l = mid + 1; else r = mid; }
+                if (l < M && sel_cls[l] == c) cand[nb + ps[tid] * M + l] = NEGINF;
+            }
+            __syncthreads();
         }
-        __syncthreads();
         // (d) K-th largest candidate: bisection over the integer image
-        const int ncand = nb + nb * C;
+        const int ncand = nb + nb * M;
         unsigned lo = 0u, hi = 0xffffffffu;                // invariant: count(key >= lo) >= K or lo == 0
         {
             int finite = 0;
@@ -185,7 +262,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             if (i < nb) {                                   // surviving leaf
                 r_node = node[i]; r_last = last[i]; r_pb = pb2[i]; r_pnb = pnb2[i];
             } else {                                        // new child of leaf b with label c
-                const int b = (i - nb) / C, c = (i - nb) - b * C;
+                const int b = (i - nb) / M, c = WIDE ? sel_cls[(i - nb) - b * M] : (i - nb) - b * M;
                 const int id = atomicAdd(&s_misc[1], 1);
                 npar[id] = node[b]; nlab[id] = (short)c;
                 r_node = id; r_last = c; r_pb = NEGINF; r_pnb = r_tot;
@@ -196,13 +273,13 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             node2[tid] = r_node; last2[tid] = r_last; pb2[tid] = r_pb; pnb2[tid] = r_pnb; tot2[tid] = r_tot;
             nslot[r_node] = tid;
         }
-        for (int i = tid; i < K * C; i += 256) table[i] = -1;
+        if constexpr (!WIDE) for (int i = tid; i < K * C; i += 256) table[i] = -1;
         __syncthreads();
         if (tid < nnew) {
             const int par = npar[node2[tid]];
             const int p = (par >= 0) ? nslot[par] : -1;
             ps2[tid] = p;
-            if (p >= 0) table[p * C + last2[tid]] = (short)tid;
+            if constexpr (!WIDE) if (p >= 0) table[p * C + last2[tid]] = (short)tid;
         }
         if (tid == 0) s_misc[0] = nnew;
         __syncthreads();
@@ -231,15 +308,36 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
 }
 
 static size_t beam_lds_bytes(int C, int K) {
-    size_t b = (size_t)((C + 3) & ~3) * 4 + (size_t)(K + K * C) * 4 + (size_t)((K * C + 1) & ~1) * 2 + (size_t)BEAM_MAX * 2 * 6 * 4 +
+    const size_t kc = (size_t)K * (size_t)C;
+    size_t b = (size_t)(((size_t)C + 3) & ~(size_t)3) * 4 + ((size_t)K + kc) * 4 + ((kc + 1) & ~(size_t)1) * 2 + (size_t)BEAM_MAX * 2 * 6 * 4 +
                (size_t)BEAM_MAX * 4;
     return (b + 15) & ~(size_t)15;
+}
+static size_t beam_wide_lds_bytes(int C, int K) {
+    const size_t M = (size_t)((K + 1 < C - 1) ? K + 1 : C - 1);
+    size_t b = (size_t)((C + 3) & ~3) * 4 + ((size_t)K + (size_t)K * M) * 4 + M * 4 + (size_t)BEAM_MAX * 2 * 6 * 4 + (size_t)BEAM_MAX * 4;
+    return (b + 15) & ~(size_t)15;
+}
+
+static int g_beam_engine = 0;
+extern "C" int ocr_set_beam_engine(int engine) {       // A/B + test knob: 0 = table kernel where it fits, 2 = wide kernel wherever it covers
+    if (engine != 0 && engine != 2) return OCR_ERR_INVALID;
+    g_beam_engine = engine;
+    return OCR_OK;
+}
+// 0 refused, 1 table kernel, 2 wide kernel: what ocr_ctc_beam_decode launches by
+extern "C" int ocr_ctc_beam_kernel_choice(int alphabet_size, int beam_width) {
+    if (alphabet_size < 2 || beam_width <= 0 || beam_width > BEAM_MAX) return 0;
+    const bool table = beam_lds_bytes(alphabet_size, beam_width) <= BEAM_LDS_LIMIT;
+    const bool wide = alphabet_size <= BEAM_WIDE_MAX_C && beam_wide_lds_bytes(alphabet_size, beam_width) <= BEAM_LDS_LIMIT;
+    if (g_beam_engine == 2 && wide) return 2;
+    return table ? 1 : (wide ? 2 : 0);
 }
 
 extern "C" int ocr_ctc_beam_workspace_size(int alphabet_size, int minibatch, int max_time, int beam_width, size_t* bytes) {
     if (!bytes || alphabet_size < 2 || minibatch <= 0 || max_time <= 0 || beam_width <= 0 || beam_width > BEAM_MAX)
         return OCR_ERR_INVALID;
-    if (beam_lds_bytes(alphabet_size, beam_width) > 160 * 1024) return OCR_ERR_INVALID;
+    if (ocr_ctc_beam_kernel_choice(alphabet_size, beam_width) == 0) return OCR_ERR_INVALID;
     size_t pool = (size_t)max_time * beam_width + 2;
     *bytes = (size_t)minibatch * pool * (sizeof(int) * 2 + sizeof(short));
     *bytes = (*bytes + 255) & ~(size_t)255;
@@ -261,9 +359,15 @@ extern "C" int ocr_ctc_beam_decode(const float* activations, const int* input_le
     a.node_parent = (int*)workspace;
     a.node_slot = a.node_parent + (size_t)minibatch * pool;
     a.node_label = (short*)(a.node_slot + (size_t)minibatch * pool);
-    const size_t lds = beam_lds_bytes(alphabet_size, beam_width);
-    if (ocr_allow_lds<ctc_beam_kernel>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
-    ctc_beam_kernel<<<minibatch, 256, lds, stream>>>(a);
+    if (ocr_ctc_beam_kernel_choice(alphabet_size, beam_width) == 2) {
+        const size_t lds = beam_wide_lds_bytes(alphabet_size, beam_width);
+        if (ocr_allow_lds<ctc_beam_kernel<true>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
+        ctc_beam_kernel<true><<<minibatch, 256, lds, stream>>>(a);
+    } else {
+        const size_t lds = beam_lds_bytes(alphabet_size, beam_width);
+        if (ocr_allow_lds<ctc_beam_kernel<false>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
+        ctc_beam_kernel<false><<<minibatch, 256, lds, stream>>>(a);
+    }
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }

@@ -114,6 +114,19 @@ def ctc_beam_decode(acts, input_lengths, beam_width=100, merge_repeated=True, pa
     return out, lens, nlp
 
 
+BEAM_KERNEL_NAMES = (None, "table", "wide")
+
+
+def ctc_beam_kernel_choice(alphabet_size, beam_width):
+    """'table' / 'wide': the kernel ctc_beam_decode runs at this shape under the current engine; None where it refuses (host-only query)."""
+    return BEAM_KERNEL_NAMES[nat.lib().ocr_ctc_beam_kernel_choice(int(alphabet_size), int(beam_width))]
+
+
+def set_beam_engine(engine):
+    """0 (default): table kernel where it fits, wide kernel elsewhere; 2: wide kernel wherever it covers the shape."""
+    call("ocr_set_beam_engine", int(engine))
+
+
 # ----------------------------------------------------------------------------------------------- GEMMs
 def gemm_nt(P, Q, out=None, *, M=None, N=None, K=None, ldp=None, ldq=None, ldo=None, bias=None, relu=False,
             out_f32=False, mask=None, accumulate=False, splits=1, row_group=0, row_skip=0, rowswap=None):
