@@ -15,9 +15,6 @@ is done here as:
 Arithmetic contract: bf16 storage and MFMA operands, fp32 accumulation, fp32 gate / cell / CTC / BN-statistics /
 optimiser math.  oracle/graph.py(sim_bf16=True) rounds at the same points.
 """
-import math
-
-import os
 import time
 
 import numpy as np
@@ -25,978 +22,87 @@ import torch
 
 from . import dist as ocr_dist
 from . import ops
-from ._native import NativeError
+from ._native import NativeError, call as nat_call
+from .engine_ops import (BF16, F32, I32, _env, _number, _switch, _AddOp, _AvgPoolOp, _BatchNormOp, _BiLstmOp, _ConcatOp, _ConvOp,
+                         _Conv3x3Op, _DropoutOp, _FcOp, _InputOp, _PoolOp, _ReluOp, _SoftmaxOp, _SubsampleOp, _ViewOp, _conv_op)
 from .layout import FlatLayout, execution_order, init_host_parameters
-from ._native import call as nat_call
 
-BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
-BN_EPS = 1e-3            # tf.contrib.layers.batch_norm default (reference network.py:176-178)
 ALIGN = 64               # parameter offsets are multiples of 64 elements (256 B)
 
+# Every environment variable the engine reads (through engine_ops._env / _switch / _number, nowhere else), by the moment it is read.
+# A switch is on unless it is '0' (default in brackets); tests and tools set them between those moments.
+#   read once, when the Engine is constructed
+#     OCR_FUSE_BN_STATS [1]      0: batch-norm statistics (and backward sums) by passes of their own, not from the convolutions' write-outs
+#     OCR_W9_FLUSH_MB [80]       slab megabytes after which the pending weight-gradient reductions run; 0: one reduction at the end of the body
+#     OCR_W9_DEFER [1]           0: every 3x3 weight gradient reduces its slabs right behind its own kernel (shared workspace)
+#     OCR_W9_DEFER_MAX_MB [192]  with OCR_W9_FLUSH_MB=0: total slab megabytes of a plan above which it falls back to the shared workspace
+#     OCR_TN_JOBS [1]            0: every plain weight-gradient product is a launch of its own, no paired gemm_tn3 launch
+#     OCR_TN_SIDE [0]            1: the paired launch runs on a side stream beside the main chain
+#     OCR_OVERLAP_ALLREDUCE [1]  0: data parallel without the split schedule: one all-reduce after the whole backward pass
+#     OCR_DP_GRAPH [0]           '1': the whole data-parallel step as ONE graph with captured collectives (opt-in)
+#     OCR_FORCE_ALLREDUCE [unset] any value: the RCCL call is exercised on a 1-rank group (tests)
+#     OCR_FAKE_WORLD [unset]     n: single-GPU emulation of n identical ranks (tests)
+#   read by every Engine._lower
+#     OCR_FUSE_ADD_RELU [1]      0: residual add and the relu behind it stay two passes; no batch-norm tail / mask fusion
+#     OCR_FUSE_CONV_POOL [1]     0: no max-pool in a 3x3 convolution's epilogue (pool_after)
+#     OCR_FUSE_BN_POOL [1]       0: no 1 x 2 max-pool inside the batch-norm passes (bn_pool)
+#   read by every op.alloc, i.e. per ShapePlan
+#     OCR_POOL_CODES [1]         0: layers in front of a fused max-pool keep their full-resolution y instead of routing codes
+#     OCR_CONV1_CODES [1]        0: conv1 + pool's backward recomputes the routing instead of reading saved codes
+#     OCR_CONV1_SLAB [1]         0: conv1 + pool's weight gradient by atomics instead of slabs + the merged reduction
+#     OCR_FUSE_BN_BWD [1]        0: no batch-norm backward sums from the consumer's data-gradient kernel
+#     OCR_MAX_WIDTH [320]        widest input the shared slab workspaces are sized for ahead of time
+#   read by every forward pass
+#     OCR_FUSE_ZERO [1]          0: the gradient buffer is cleared by a fill, not by conv1 + pool's launch
+#     OCR_FUSE_RINGFILL [1]      0: every persistent LSTM launch fills its own hand-off block
+#     OCR_LSTM_FUSE_X [1]        0: the BiLSTM's input projection stays a GEMM of its own
+#   read at every use (Engine._guard_on)
+#     OCR_LSTM_TIMEOUT_GUARD [1] 0: a persistent-LSTM time-out does not drop the step's update
 
-def _round_up(x, m):
-    return (x + m - 1) // m * m
 
-
-# ====================================================================================================== ops
-def _take_ring(sp, key):
-    """True once per fill: the hand-off block `key` still holds the all-ones pattern the conv1 + pool launch of THIS forward pass wrote.
-    The persistent LSTM launch that asks consumes it — a second launch on the same block (a repeated backward pass without a new
-    training forward) gets False and fills the block itself."""
-    ready = getattr(sp, 'rings_ready', None)
-    if not ready or key not in ready:
-        return False
-    ready.discard(key)
-    return True
-
-
-class _Op(object):
-    mask_in_consumer = False      # True: output has a fused ReLU whose backward the consumer must apply
-
-    def __init__(self, eng, node, prev):
-        self.eng, self.node, self.prev, self.name = eng, node, prev, node.name
-        self.key = node.name          # buffer key; made unique by Engine._lower (the reference reuses layer names)
-        self.inputs = [prev]
-        self.consumers = 0            # how many ops read this op's output (residual graphs: > 1)
-
-    def grad_owner(self):             # the op whose dy buffer really receives gradients for this output (views forward it)
-        return self
-
-    def out_shape(self, in_shape):
-        raise NotImplementedError
-
-    def alloc(self, sp, in_shape):
-        pass
-
-    def refresh(self):            # re-pack work that is not expressible as a pack job
-        pass
-
-    def pack_jobs(self):          # bf16 operand re-packs after a parameter update (executed by ONE launch)
-        return []
-
-    def shadow_params(self):      # variables whose plain bf16 copy (same layout, Engine.shadow) this op reads
-        return []
-
-    def fwd(self, sp):
-        pass
-
-    def bwd(self, sp):
-        pass
-
-    # gradient w.r.t. this op's output (written by the consumer)
-    def y(self, sp):
-        return sp.buf[self.key + '/y']
-
-    def dy(self, sp):
-        return sp.buf[self.key + '/dy']
-
-
-class _InputOp(_Op):
-    def __init__(self, eng):
-        self.eng, self.name, self.prev, self.node = eng, 'data', None, None
-        self.key = 'data'
-        self.inputs, self.consumers = [], 0
-
-    def y(self, sp):
-        return sp.x
-
-    def dy(self, sp):
-        return None
-
-
-class _ConvOp(_Op):
-    def __init__(self, eng, node, prev):
-        super(_ConvOp, self).__init__(eng, node, prev)
-        a = node.attrs
-        self.kh, self.kw, self.co, self.ci = a['k_h'], a['k_w'], a['c_o'], a['c_i']
-        self.bn, self.relu, self.biased, self.padding = a['bn'], a['relu'], a['biased'], a['padding']
-        # strides: the op itself always runs at stride 1; Engine._lower appends a _SubsampleOp (a strided convolution is the
-        # stride-1 convolution evaluated at every s-th position)
-        if self.ci == 1:
-            if (self.kh, self.kw, self.padding) != (3, 3, 'SAME') or self.co != 64 or self.bn or not self.biased:
-                raise NotImplementedError('%s: the single-channel input conv is lowered for 3x3 SAME, 64 filters' % self.name)
-            self.kind = 'c1'
-        elif (self.kh, self.kw, self.padding) == (3, 3, 'SAME'):
-            if self.ci % 32 or self.co % 8:
-                raise NotImplementedError('%s: 3x3 conv needs C_in %% 32 == 0 and C_out %% 8 == 0' % self.name)
-            self.kind = '3x3'
-        elif (self.kh, self.kw) == (1, 1):
-            if self.ci % 8 or self.co % 8:
-                raise NotImplementedError('%s: 1x1 conv needs C_in %% 8 == 0 and C_out %% 8 == 0' % self.name)
-            self.kind = '1x1'           # a plain GEMM over pixels
-        elif self.padding == 'VALID':
-            self.kind = 'full'          # kernel spans the whole feature axis -> plain GEMM over overlapping rows
-        else:
-            raise NotImplementedError('%s: %dx%d %s convolution is not lowered' % (self.name, self.kh, self.kw, self.padding))
-        self.mask_in_consumer = self.relu and not self.bn
-        dev = eng.device
-        K = self.kh * self.kw * self.ci
-        if self.kind != 'c1':
-            self.wpack = torch.empty((self.co, K), dtype=BF16, device=dev)
-            if self.kind == '3x3' and prev.dy_needed():
-                self.wdgrad = torch.empty((self.ci, 9 * self.co), dtype=BF16, device=dev)
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        N, W, H = s[0], s[1], s[2]
-        if self.kind == 'full':
-            if self.kw != H:
-                raise NotImplementedError('%s: VALID conv is lowered only when k_w equals the feature-axis size '
-                                          '(got k_w=%d, H=%d)' % (self.name, self.kw, H))
-            return (N, W - self.kh + 1, 1, self.co)
-        return (N, W, H, self.co)
-
-    fused_pool = None          # set by Engine._lower: conv1 + ReLU + 2x2 max-pool run as one kernel, no full-res activation
-    tail_into = None           # set by Engine._lower: (add op, the add's other input) — this conv's batch-norm apply pass also does the
-                               # residual add + relu and writes the add's output (the add's forward is then a no-op)
-    mask_from = None           # set by Engine._lower: the fused add + relu that is this (BN, no ReLU) conv's only consumer: its batch-norm
-                               # backward reads the add's gradient and applies the add's ReLU mask itself (no masked copy pass)
-    bn_pool = None             # set by Engine._lower: the 1 x 2 max-pool that is this batch-norm layer's only consumer (written by the BN apply
-                               # pass; its gradient is routed inside the BN backward passes)
-    pool_after = None          # set by Engine._lower: the max-pool that follows this 3x3 conv + ReLU; where the shape allows, the conv's
-                               # epilogue writes the pooled tensor too (the full-resolution output is still kept for the backward pass)
-
-    def alloc(self, sp, s):
-        o = self.out_shape(s)
-        dev = self.eng.device
-        sp.shape[self.key] = (s, o)
-        if self.fused_pool is not None:
-            if self.co == 64 and self.eng.defer_w9 and os.environ.get('OCR_CONV1_SLAB', '1') != '0':
-                # the backward kernel's per-block partial sums (no atomics); two jobs of the merged slab reduction add them
-                sp.buf[self.key + '/slab'] = torch.empty((ops.conv1_pool_bwd_slab_rows(s[0], s[1], s[2]), 640), dtype=F32, device=dev)
-            if self.co == 64 and os.environ.get('OCR_CONV1_CODES', '1') != '0':
-                # pool routing + ReLU bits saved by the training forward pass (4 bits per pooled output) for the backward pass
-                sp.buf[self.key + '/codes'] = torch.empty((s[0] * (s[1] // 2) * (s[2] // 2), 8), dtype=torch.int32, device=dev)
-            return
-        # A max-pool that is this layer's only consumer (bn_pool: behind the batch norm; pool_after: written by the convolution's epilogue): a
-        # training forward pass writes the pool's routing codes (4 bits per pooled output: which element of the window won, and its ReLU
-        # bit — conv1's format) instead of the full-resolution y, whose only readers were backward passes looking for exactly that
-        # (OCR_POOL_CODES=0: keep y).  No y buffer then: an inference forward on this plan allocates it on first use (_ConvOp.y).
-        windows = 0
-        if os.environ.get('OCR_POOL_CODES', '1') != '0':
-            p = self.pool_after
-            if self.bn_pool is not None:
-                windows = o[0] * o[1] * o[2] // 2
-            elif (p is not None and ops.conv3x3_pool_supported(s[0], s[1], s[2], self.ci, self.co, p.kw_t, p.kh_f)
-                    and ops.conv3x3_pool_codes_supported(s[0], s[1], s[2], self.ci, self.co, p.kw_t, p.kh_f)):
-                windows = o[0] * (o[1] // p.kw_t) * (o[2] // p.kh_f)
-        if windows:
-            sp.buf[self.key + '/pool_codes'] = torch.empty((windows, self.co // 8), dtype=torch.int32, device=dev)
-        else:
-            sp.buf[self.key + '/y'] = torch.empty(o, dtype=BF16, device=dev)
-        sp.buf[self.key + '/dy'] = torch.empty(o, dtype=BF16, device=dev)
-        if self.bn:
-            sp.buf[self.key + '/z'] = torch.empty(o, dtype=BF16, device=dev)
-            sp.buf[self.key + '/dz'] = torch.empty(o, dtype=BF16, device=dev)
-            sp.buf[self.key + '/mean'] = torch.empty(self.co, dtype=F32, device=dev)
-            sp.buf[self.key + '/rstd'] = torch.empty(self.co, dtype=F32, device=dev)
-            sp.buf[self.key + '/bnws'] = ops.bn_workspace(o[0] * o[1] * o[2], self.co, dev)
-            # batch-norm statistics from the convolution's own epilogue where a plane-layout kernel takes the shape (partial rows into the
-            # BN workspace: it must hold them), else a statistics pass over z
-            rows = 0
-            if self.kind == '3x3' and self.eng.fuse_bn_stats:
-                rows = ops.conv3x3_stats_rows(s[0], s[1], s[2], self.ci, self.co, bias=self.biased)
-                if rows * 2 * self.co * 4 > sp.buf[self.key + '/bnws'].numel() - 2 * self.co * 8:
-                    rows = 0
-            sp.bn_stat_rows = getattr(sp, 'bn_stat_rows', {})
-            sp.bn_stat_rows[self.key] = rows
-        if self.kind == 'full':
-            N, W, H, C = s
-            sp.buf[self.key + '/col'] = torch.empty((N * o[1], self.kh * H * C), dtype=BF16, device=dev)
-        if self.pool_after is not None:
-            p = self.pool_after
-            sp.fused_pools = getattr(sp, 'fused_pools', set())
-            if ops.conv3x3_pool_supported(s[0], s[1], s[2], self.ci, self.co, p.kw_t, p.kh_f):
-                sp.fused_pools.add(p.key)
-        if self.kind == '3x3' and hasattr(self, 'wdgrad') and self.eng.fuse_bn_stats and os.environ.get('OCR_FUSE_BN_BWD', '1') != '0':
-            # the producer is a batch-norm + ReLU convolution feeding only this one: its batch-norm BACKWARD sums (and its ReLU mask) are
-            # taken by this layer's data-gradient kernel (conv_k3's write-out), where a plane-layout kernel takes the shape
-            p = self.prev
-            rows = 0
-            if (isinstance(p, _ConvOp) and p.bn and p.relu and p.consumers == 1 and p.tail_into is None and p.mask_from is None
-                    and p.bn_pool is None and p.kind != 'c1'):
-                rows = ops.conv3x3_bnbwd_rows(s[0], s[1], s[2], self.co, self.ci)
-                if rows * 2 * self.ci * 4 > sp.buf[p.key + '/bnws'].numel() - 2 * self.ci * 8:
-                    rows = 0
-            sp.bn_bwd_rows = getattr(sp, 'bn_bwd_rows', {})
-            if isinstance(p, _ConvOp):
-                # the producer's backward sums come EITHER from this layer's data-gradient write-out (partial rows) OR from its own passes
-                # routing a pooled gradient — never both: ocr_bn_train_bwd2 takes one form per launch
-                assert p.bn_pool is None or not rows, (p.key, rows)
-                sp.bn_bwd_rows[p.key] = rows
-        if self.kind == '3x3':      # scratch of the slab weight-gradient kernel
-            need = ops.conv3x3_wgrad_workspace_bytes(s[0], s[1], s[2], self.ci, self.co)
-            have = sp.buf.get('wgrad_ws')
-            if need and self.eng.defer_w9:
-                # one buffer PER LAYER: the slabs stay until the end of the backward pass, where ONE launch reduces all layers'
-                # (Engine._flush_w9) — ~20 MB per layer of 288 GB against four dependent launches less per step
-                # ... shared by the plans of an engine (plans run one at a time on one stream and no slab outlives its backward body): a
-                # variable-width run makes one plan per padded width — a narrower plan takes a view of the widest workspace allocated so
-                # far instead of slabs of its own (ADVICE r4: 9-61 plans x ~0.4 GB for the deep net otherwise)
-                pool = self.eng.w9_ws_pool
-                have_ws = pool.get(self.key)
-                if have_ws is None or have_ws.numel() < need:
-                    # sized ONCE for the widest batch this engine is expected to see (ADVICE r5: plans created in ascending width order — the usual
-                    # case for variable-width batches — each found the pool too small and allocated a block of their own): the slab bytes of a
-                    # layer grow with the split count, which is capped, so the need at OCR_MAX_WIDTH (default 320 = configs[3]'s widest) bounds them
-                    wmax = max(int(os.environ.get('OCR_MAX_WIDTH', '320')), sp.W)
-                    scale = max(1, wmax // sp.W + (1 if wmax % sp.W else 0))
-                    big = need
-                    if scale > 1:
-                        big = max(need, ops.conv3x3_wgrad_workspace_bytes(s[0], s[1] * scale, s[2], self.ci, self.co))
-                    have_ws = pool[self.key] = torch.empty(big, dtype=torch.uint8, device=dev)      # (older plans keep the block their graphs captured)
-                sp.buf[self.key + '/w9ws'] = have_ws[:need]
-            elif need and (have is None or have.numel() < need):     # one buffer per plan, shared by all layers (one stream)
-                sp.buf['wgrad_ws'] = torch.empty(need, dtype=torch.uint8, device=dev)
-
-    def y(self, sp):
-        t = sp.buf.get(self.key + '/y')
-        if t is None:       # a plan whose training steps keep routing codes instead (alloc): an inference forward is the first to need it
-            t = sp.buf[self.key + '/y'] = torch.empty(sp.shape[self.key][1], dtype=BF16, device=self.eng.device)
-        return t
-
-    def shadow_params(self):
-        return [self.name + '/weights'] if self.kind in ('1x1', 'full') else []
-
-    def pack_jobs(self):
-        if self.kind == 'c1':
-            return []
-        w = self.eng.param(self.name + '/weights')
-        K = self.kh * self.kw * self.ci
-        jobs = [dict(type=0, R=K, Cc=self.co, ldin=self.co, src=w, dst=self.wpack)]
-        if hasattr(self, 'wdgrad'):
-            jobs.append(dict(type=1, R=self.ci, Cc=self.co, src=w, dst=self.wdgrad, n=w.numel()))
-        return jobs
-
-    def fwd(self, sp):
-        e = self.eng
-        x = self.prev.y(sp)
-        s, o = sp.shape[self.key]
-        bias = e.param(self.name + '/biases') if self.biased else None
-        if self.fused_pool is not None:
-            zero, e._zero_pending = (e.grads if e._zero_pending else None), False     # the gradient buffer's clear rides on this launch
-            codes = sp.buf.get(self.key + '/codes') if e.training else None
-            ones, e._ones_pending = e._ones_pending, None                              # ... and so does the fill of the LSTM hand-off blocks
-            ops.conv1_pool_fwd(x, e.param(self.name + '/weights'), bias, out=self.fused_pool.y(sp), zero=zero, codes=codes, ones=ones)
-            # every hand-off block of the plan is armed now; each persistent launch consumes (and thereby dirties) its own block ONCE
-            sp.rings_ready = set(getattr(sp, 'lstm_sync_keys', ())) if ones is not None else set()
-            sp.rings_armed = ones is not None         # (what the last forward pass did; rings_ready is consumed by the launches)
-            return
-        codes = sp.buf.get(self.key + '/pool_codes') if e.training else None
-        y = None if codes is not None else self.y(sp)
-        if self.kind == 'c1':
-            ops.conv1_fwd(x, e.param(self.name + '/weights'), bias, relu=self.relu, out=y)
-            return
-        tgt = sp.buf[self.key + '/z'] if self.bn else y
-        relu_now = self.relu and not self.bn
-        if self.kind == '3x3' and self.pool_after is not None and self.pool_after.key in sp.fused_pools:
-            p = self.pool_after
-            if codes is not None:
-                ops.conv3x3_relu_pool_codes(x, self.wpack.view(self.co, 3, 3, self.ci), None, p.y(sp), codes, bias, p.kw_t, p.kh_f)
-            else:
-                ops.conv3x3_relu_pool(x, self.wpack.view(self.co, 3, 3, self.ci), y, p.y(sp), bias, p.kw_t, p.kh_f)
-        elif self.kind == '3x3' and self.bn and sp.bn_stat_rows[self.key]:
-            ops.conv3x3_stats(x, self.wpack.view(self.co, 3, 3, self.ci), tgt, sp.buf[self.key + '/bnws'], bias=bias)
-        elif self.kind == '3x3':
-            ops.conv3x3(x, self.wpack.view(self.co, 3, 3, self.ci), out=tgt, bias=bias, relu=relu_now)
-        elif self.kind == '1x1':
-            Mx = s[0] * s[1] * s[2]
-            ops.gemm_nt(x.view(Mx, self.ci), self.wpack, out=tgt.view(Mx, self.co), bias=bias, relu=relu_now)
-        else:
-            N, W, H, C = s
-            Wo = o[1]
-            ops.gemm_nt(x, self.wpack, out=tgt.view(N * Wo, self.co), M=N * Wo, N=self.co, K=self.kh * H * C,
-                        ldp=H * C, ldq=self.kh * H * C, bias=bias, relu=relu_now, row_group=Wo, row_skip=self.kh - 1)
-        if self.bn:
-            M = o[0] * o[1] * o[2]
-            res, relu = None, self.relu
-            if self.tail_into is not None:          # y_add = relu(bf16(bn(z)) + other input): written straight into the add's buffer
-                add, other = self.tail_into
-                y, res, relu = add.y(sp), other.y(sp).view(M, self.co), True
-            pooled = self.bn_pool.y(sp).view(M // 2, self.co) if self.bn_pool is not None else None
-            ops.bn_train_fwd(tgt.view(M, self.co), e.param('%s/%s/gamma' % (self.name, self.name)),
-                             e.param('%s/%s/beta' % (self.name, self.name)), BN_EPS, relu,
-                             sp.buf[self.key + '/bnws'], out=None if y is None else y.view(M, self.co),
-                             save_mean=sp.buf[self.key + '/mean'], save_rstd=sp.buf[self.key + '/rstd'], residual=res,
-                             partial_rows=sp.bn_stat_rows[self.key], pooled=pooled, codes=codes)
-
-    def bwd(self, sp):
-        e = self.eng
-        if self.fused_pool is not None:     # pool routing + ReLU mask + weight gradient in one recomputing pass
-            slab = sp.buf.get(self.key + '/slab')
-            if slab is not None:
-                ops.conv1_pool_bwd_slab(self.prev.y(sp), e.param(self.name + '/weights'), e.param(self.name + '/biases'), self.fused_pool.dy(sp),
-                                        slab, codes=sp.buf.get(self.key + '/codes'))
-                S = slab.shape[0]
-                for dst, off, n4 in ((e.grad(self.name + '/weights'), 0, 144), (e.grad(self.name + '/biases'), 576, 16)):
-                    job = np.zeros(1, dtype=e.W9_JOB_DTYPE)
-                    job['dw'], job['part'], job['n4'], job['slab4'] = dst.data_ptr(), slab.data_ptr() + 4 * off, n4, 160
-                    job['S'], job['rows'], job['Cout'] = S, 8, 64
-                    sp.w9_pending.append((job.tobytes(), (n4 + 31) // 32))          # 256 / rows = 32 float4 columns per block
-                return
-            ops.conv1_pool_bwd(self.prev.y(sp), e.param(self.name + '/weights'), e.param(self.name + '/biases'),
-                               self.fused_pool.dy(sp), e.grad(self.name + '/weights'), e.grad(self.name + '/biases'),
-                               codes=sp.buf.get(self.key + '/codes'))
-            return
-        s, o = sp.shape[self.key]
-        x = self.prev.y(sp)
-        dy = self.dy(sp)                    # already ReLU-masked by the consumer unless this layer has BN
-        M = o[0] * o[1] * o[2]
-        dz = dy
-        if self.bn:
-            dz = sp.buf[self.key + '/dz']
-            codes = sp.buf.get(self.key + '/pool_codes')
-            ymask, relu = (self.y(sp) if codes is None else None), self.relu
-            if self.mask_from is not None:          # gradient and ReLU mask straight from the residual add + relu behind this layer
-                dy, ymask, relu = self.mask_from.dy(sp), self.mask_from.y(sp), True
-            dy2 = dy.view(M, self.co)
-            if self.bn_pool is not None:            # the pooled gradient, routed by the passes themselves
-                dy2 = self.bn_pool.dy(sp).view(M // 2, self.co)
-            ops.bn_train_bwd(sp.buf[self.key + '/z'].view(M, self.co), None if ymask is None else ymask.view(M, self.co), dy2,
-                             e.param('%s/%s/gamma' % (self.name, self.name)), sp.buf[self.key + '/mean'],
-                             sp.buf[self.key + '/rstd'], e.grad('%s/%s/gamma' % (self.name, self.name)),
-                             e.grad('%s/%s/beta' % (self.name, self.name)), relu, sp.buf[self.key + '/bnws'],
-                             out=dz.view(M, self.co), pooled_dy=self.bn_pool is not None,
-                             partial_rows=getattr(sp, 'bn_bwd_rows', {}).get(self.key, 0), codes=codes)
-        dw = e.grad(self.name + '/weights')
-        db = e.grad(self.name + '/biases') if self.biased else None
-        if self.kind == 'c1':
-            ops.conv1_wgrad(x, dz, dw, db)
-            return
-        pmask = self.prev.y(sp) if self.prev.mask_in_consumer else None
-        if self.kind == '3x3':
-            own_ws = sp.buf.get(self.key + '/w9ws')
-            if own_ws is not None:      # slab kernel now, the reduction with the other layers' at the end of the pass
-                job, nblk = ops.conv3x3_wgrad_deferred(x, dz, dw, db, own_ws)
-                if job is not None:
-                    sp.w9_pending.append((job, nblk))
-                    sp.w9_pending_bytes = getattr(sp, 'w9_pending_bytes', 0) + own_ws.numel()
-                    if e.w9_flush_bytes and sp.w9_pending_bytes >= e.w9_flush_bytes:
-                        e._flush_w9(sp)         # (knob OCR_W9_FLUSH_MB: reduce while the slabs are still in the Infinity Cache)
-            else:
-                ops.conv3x3_wgrad(x, dz, dw, dbias=db, workspace=sp.buf.get('wgrad_ws'))   # bias gradient rides on the same pass
-            # a producer with several consumers (residual graphs): where the halo kernel runs, its epilogue adds to what was already
-            # delivered instead of writing a scratch tensor that a second pass adds
-            pdy, finish, acc = e.grad_dst_acc(sp, self.prev, ops.conv3x3_accum_supported(o[0], o[1], o[2], self.co, self.ci))
-            if pdy is not None:
-                p = self.prev
-                if getattr(sp, 'bn_bwd_rows', {}).get(p.key, 0) and not acc:
-                    ops.conv3x3_dgrad_bnbwd(dz, self.wdgrad.view(self.ci, 3, 3, self.co), pdy, p.y(sp), sp.buf[p.key + '/z'],
-                                            sp.buf[p.key + '/mean'], sp.buf[p.key + '/rstd'], sp.buf[p.key + '/bnws'])
-                else:
-                    ops.conv3x3(dz, self.wdgrad.view(self.ci, 3, 3, self.co), out=pdy, mask=pmask, accumulate=acc)
-                finish()
-            return
-        pdy, finish = e.grad_dst(sp, self.prev)
-        if self.kind == '1x1':
-            ops.gemm_tn(x.view(M, self.ci), dz.view(M, self.co), dw.view(self.ci, self.co), colsum=db)
-            if pdy is not None:
-                wsh = e.shadow(self.name + '/weights').view(self.ci, self.co)      # Q[n = ci][k = co]
-                ops.gemm_nt(dz.view(M, self.co), wsh, out=pdy.view(M, self.ci),
-                            mask=None if pmask is None else pmask.view(M, self.ci))
-                finish()
-        else:
-            N, W, H, C = s
-            Wo = o[1]
-            K = self.kh * H * C
-            dz2, dw2 = dz.view(M, self.co), dw.view(K, self.co)
-            e.tn_push(sp, ops.tn_job(x, H * C, dz2, self.co, dw2, self.co, M, K, self.co, row_group=Wo, row_skip=self.kh - 1, colsum=db),
-                      (x, dz2, dw2, db),
-                      lambda: ops.gemm_tn(x, dz2, dw2, Mk=M, I=K, J=self.co, lda=H * C, ldb=self.co,
-                                          ldo=self.co, row_group=Wo, row_skip=self.kh - 1, colsum=db))
-            if pdy is not None:
-                if pmask is not None or self.kh != 2:
-                    raise NotImplementedError('%s: data gradient of a full-height VALID conv is lowered for k_h = 2 '
-                                              'behind a non-ReLU producer' % self.name)
-                col = sp.buf[self.key + '/col']
-                wsh = e.shadow(self.name + '/weights').view(K, self.co)      # [K][co] bf16, k = co contiguous
-                ops.gemm_nt(dz.view(M, self.co), wsh, out=col, M=M, N=K, K=self.co)
-                ops.conv5_col2im(col, pdy, N, W, H * C)
-                finish()
-
-
-class _FcOp(_ConvOp):
-    """Network.fc (network.py:415-447) on a row tensor [N, T, d]: y = relu?(x W + b) over the last axis = the GEMMs of a 1 x 1 convolution
-    (`weights [dim, num_out]` has the memory layout of a [1, 1, dim, num_out] filter), so forward, data gradient, weight gradient, bf16 shadow and
-    re-pack are _ConvOp's '1x1' paths on the flattened rows."""
-
-    def __init__(self, eng, node, prev):
-        super(_FcOp, self).__init__(eng, node, prev)
-        assert self.kind == '1x1'
-
-    def out_shape(self, s):
-        return tuple(s[:-1]) + (self.co,)
-
-    def alloc(self, sp, s):
-        o = self.out_shape(s)
-        rows = int(np.prod(s[:-1]))
-        sp.shape[self.key] = ((rows, 1, 1, s[-1]), (rows, 1, 1, self.co))      # what the 1x1 paths multiply out
-        sp.buf[self.key + '/y'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-        sp.buf[self.key + '/dy'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-
-
-class _PoolOp(_Op):
-    def __init__(self, eng, node, prev):
-        super(_PoolOp, self).__init__(eng, node, prev)
-        a = node.attrs
-        # reference argument order is (k_h, k_w, s_h, s_w) with TF "height" = our time axis W
-        self.kw_t, self.kh_f = a['k_h'], a['k_w']
-        if (a['s_h'], a['s_w']) != (a['k_h'], a['k_w']) or self.kw_t not in (1, 2) or self.kh_f not in (1, 2):
-            raise NotImplementedError('%s: max-pool is lowered for window == stride in {1,2}' % self.name)
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        N, W, H, C = s
-        if W % self.kw_t or H % self.kh_f:
-            raise NotImplementedError('%s: pooled axes must divide evenly (W=%d, H=%d)' % (self.name, W, H))
-        return (N, W // self.kw_t, H // self.kh_f, C)
-
-    def alloc(self, sp, s):
-        o = self.out_shape(s)
-        sp.shape[self.key] = (s, o)
-        sp.buf[self.key + '/y'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-        sp.buf[self.key + '/dy'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-
-    fused_into = None          # the conv1 op that computes this pool's output itself
-    bn_fused_into = None       # the batch-norm conv whose apply pass writes this pool's output and whose backward passes route its gradient
-
-    def fwd(self, sp):
-        if self.bn_fused_into is not None:
-            return
-        if self.fused_into is None and self.key not in getattr(sp, 'fused_pools', ()):      # else: written by the producing conv's epilogue
-            ops.maxpool_fwd(self.prev.y(sp), self.kw_t, self.kh_f, out=self.y(sp))
-
-    def bwd(self, sp):
-        if self.fused_into is not None or self.bn_fused_into is not None:
-            return
-        pdy, finish = self.eng.grad_dst(sp, self.prev)
-        if pdy is not None:
-            codes = sp.buf.get(self.prev.key + '/pool_codes') if getattr(self.prev, 'pool_after', None) is self else None
-            if codes is not None:       # the producing convolution's training forward left routing codes and no full-resolution output
-                ops.maxpool_bwd_codes(codes, self.dy(sp), self.kw_t, self.kh_f, self.prev.mask_in_consumer, out=pdy)
-            else:
-                ops.maxpool_bwd(self.prev.y(sp), self.dy(sp), self.kw_t, self.kh_f, self.prev.mask_in_consumer, out=pdy)
-            finish()
-
-
-class _ViewOp(_Op):
-    """reshape_squeeze_layer / dropout(identity): no data movement, shares the producer's buffers."""
-
-    def __init__(self, eng, node, prev):
-        super(_ViewOp, self).__init__(eng, node, prev)
-        self.mask_in_consumer = prev.mask_in_consumer
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        if self.node.op == 'reshape_squeeze':
-            N, A, B, C = s
-            return (N, A * B, C)
-        return s
-
-    def alloc(self, sp, s):
-        sp.shape[self.key] = (s, self.out_shape(s))
-
-    def y(self, sp):
-        return self.prev.y(sp).view(sp.shape[self.key][1])
-
-    def dy(self, sp):
-        d = self.prev.dy(sp)
-        return None if d is None else d.view(sp.shape[self.key][1])
-
-    def grad_owner(self):
-        return self.prev.grad_owner()
-
-
-class _AddOp(_Op):
-    """Network.add (network.py:461-463): element-wise sum of two feature maps (residual connections)."""
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        return s
-
-    def alloc(self, sp, s):
-        sp.shape[self.key] = (s, s)
-        sp.buf[self.key + '/y'] = torch.empty(s, dtype=BF16, device=self.eng.device)
-        sp.buf[self.key + '/dy'] = torch.empty(s, dtype=BF16, device=self.eng.device)
-
-    relu = False               # True: the Network.relu that follows (its only consumer) is computed here, y = relu(a + b)
-
-    fwd_by = None              # the producing conv whose batch-norm apply pass writes this op's output (Engine._lower)
-
-    def fwd(self, sp):
-        if self.fwd_by is None:
-            ops.eltwise(3 if self.relu else 0, self.inputs[0].y(sp), self.inputs[1].y(sp), self.y(sp))
-
-    def bwd(self, sp):
-        for p in self.inputs:
-            if getattr(p, 'mask_from', None) is self:
-                continue                            # that producer's batch-norm backward reads dy / y of this op directly
-            self.eng.deliver(sp, p, self.dy(sp), mask=self.y(sp) if self.relu else None)
-
-
-class _ReluOp(_Op):
-    """Network.relu (network.py:340-341) as a stand-alone layer (after a residual add)."""
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        return s
-
-    fused_into = None          # the _AddOp that computes relu(a + b) itself: this op is then a view of it (no buffers, no launches)
-
-    def alloc(self, sp, s):
-        sp.shape[self.key] = (s, s)
-        if self.fused_into is None:
-            sp.buf[self.key + '/y'] = torch.empty(s, dtype=BF16, device=self.eng.device)
-            sp.buf[self.key + '/dy'] = torch.empty(s, dtype=BF16, device=self.eng.device)
-
-    def y(self, sp):
-        return self.fused_into.y(sp) if self.fused_into is not None else sp.buf[self.key + '/y']
-
-    def dy(self, sp):
-        return self.fused_into.dy(sp) if self.fused_into is not None else sp.buf[self.key + '/dy']
-
-    def grad_owner(self):
-        return self.fused_into.grad_owner() if self.fused_into is not None else self
-
-    def fwd(self, sp):
-        if self.fused_into is None:
-            ops.eltwise(1, self.prev.y(sp), None, self.y(sp))
-
-    def bwd(self, sp):
-        if self.fused_into is None:
-            self.eng.deliver(sp, self.prev, self.dy(sp), mask=self.y(sp))
-
-
-class _SubsampleOp(_Op):
-    """Second half of a strided convolution (Network.conv / conv_single with s_h, s_w > 1, network.py:193-216): picks every
-    s-th position of the stride-1 result.  TF SAME: out = ceil(in / s), pad_before = max((out-1) s + k - in, 0) // 2, so output
-    o is the stride-1 output at o s + (k-1)//2 - pad_before."""
-
-    def __init__(self, eng, node, prev):
-        super(_SubsampleOp, self).__init__(eng, node, prev)
-        a = node.attrs
-        self.sw, self.sh, self.kw, self.kh = a['s_h'], a['s_w'], a['k_h'], a['k_w']      # reference "height" = our time axis W
-        if a['padding'] != 'SAME':
-            raise NotImplementedError('%s: strided convolution is lowered for SAME padding' % self.name)
-
-    def dy_needed(self):
-        return True
-
-    @staticmethod
-    def _geom(n, k, s):
-        out = -(-n // s)
-        before = max((out - 1) * s + k - n, 0) // 2
-        return out, (k - 1) // 2 - before
-
-    def out_shape(self, s):
-        N, W, H, C = s
-        Wo, self.ow = self._geom(W, self.kw, self.sw)
-        Ho, self.oh = self._geom(H, self.kh, self.sh)
-        return (N, Wo, Ho, C)
-
-    def alloc(self, sp, s):
-        o = self.out_shape(s)
-        sp.shape[self.key] = (s, o)
-        sp.buf[self.key + '/y'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-        sp.buf[self.key + '/dy'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-
-    def fwd(self, sp):
-        (N, W, H, C), (_, Wo, Ho, _) = sp.shape[self.key]
-        ops.subsample(self.prev.y(sp), self.y(sp), N, W, H, C, Wo, Ho, self.sw, self.sh, self.ow, self.oh)
-
-    def bwd(self, sp):
-        (N, W, H, C), (_, Wo, Ho, _) = sp.shape[self.key]
-        pdy, finish = self.eng.grad_dst(sp, self.prev)
-        if pdy is not None:
-            ops.subsample(self.dy(sp), pdy, N, W, H, C, Wo, Ho, self.sw, self.sh, self.ow, self.oh, backward=True)
-            if self.prev.mask_in_consumer:
-                ops.eltwise(2, pdy, self.prev.y(sp), pdy)
-            finish()
-
-
-class _BatchNormOp(_Op):
-    """Network.batch_normalization (network.py:466-473): batch statistics when is_training, else the stored moving ones."""
-
-    def __init__(self, eng, node, prev):
-        super(_BatchNormOp, self).__init__(eng, node, prev)
-        self.relu, self.training = node.attrs['relu'], node.attrs['is_training']
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        return s
-
-    def alloc(self, sp, s):
-        dev, C = self.eng.device, s[-1]
-        sp.shape[self.key] = (s, s)
-        sp.buf[self.key + '/y'] = torch.empty(s, dtype=BF16, device=dev)
-        sp.buf[self.key + '/dy'] = torch.empty(s, dtype=BF16, device=dev)
-        sp.buf[self.key + '/dx'] = torch.empty(s, dtype=BF16, device=dev)
-        if self.training:
-            M = int(np.prod(s[:-1]))
-            sp.buf[self.key + '/mean'] = torch.empty(C, dtype=F32, device=dev)
-            sp.buf[self.key + '/rstd'] = torch.empty(C, dtype=F32, device=dev)
-            sp.buf[self.key + '/bnws'] = ops.bn_workspace(M, C, dev)
-
-    def _x(self, sp):
-        if self.prev.mask_in_consumer:
-            raise NotImplementedError('%s: batch_normalization behind a fused-ReLU convolution is not lowered' % self.name)
-        return self.prev.y(sp)
-
-    def fwd(self, sp):
-        e, (s, _) = self.eng, sp.shape[self.key]
-        C = s[-1]
-        M = int(np.prod(s[:-1]))
-        x, y = self._x(sp).view(M, C), self.y(sp).view(M, C)
-        if self.training:
-            ops.bn_train_fwd(x, e.param(self.name + '/gamma'), e.param(self.name + '/beta'), BN_EPS, self.relu, sp.buf[self.key + '/bnws'],
-                             out=y, save_mean=sp.buf[self.key + '/mean'], save_rstd=sp.buf[self.key + '/rstd'])
-        else:
-            ops.bn_infer_fwd(x, e.param(self.name + '/gamma'), e.param(self.name + '/beta'), e.param(self.name + '/moving_mean'),
-                             e.param(self.name + '/moving_variance'), BN_EPS, self.relu, y)
-
-    def bwd(self, sp):
-        e, (s, _) = self.eng, sp.shape[self.key]
-        C = s[-1]
-        M = int(np.prod(s[:-1]))
-        x, y, dy, dx = self._x(sp).view(M, C), self.y(sp).view(M, C), self.dy(sp).view(M, C), sp.buf[self.key + '/dx'].view(M, C)
-        if self.training:
-            ops.bn_train_bwd(x, y, dy, e.param(self.name + '/gamma'), sp.buf[self.key + '/mean'], sp.buf[self.key + '/rstd'],
-                             e.grad(self.name + '/gamma'), e.grad(self.name + '/beta'), self.relu, sp.buf[self.key + '/bnws'], out=dx)
-        else:
-            ops.bn_infer_bwd(x, y, dy, e.param(self.name + '/gamma'), e.param(self.name + '/moving_mean'),
-                             e.param(self.name + '/moving_variance'), e.grad(self.name + '/gamma'), e.grad(self.name + '/beta'), BN_EPS,
-                             self.relu, dx)
-        e.deliver(sp, self.prev, sp.buf[self.key + '/dx'])
-
-
-class _DropoutOp(_Op):
-    """Network.dropout = tf.nn.dropout(x, keep_prob) (network.py:626-628).  keep_prob is the layer's own argument: the network's
-    keep_prob input slot (what the shipped graphs pass) takes the value the driver feeds — 0.5 in training steps (train.py:126), 1.0
-    otherwise (train.py:156, test.py:75): Engine.train_keep_prob / inference = 1 — and a NUMBER written in the graph is a constant of
-    the graph, applied in training and inference alike, as tf.nn.dropout does with a Python float (it used to be ignored).
-    The mask is a hash of (layer name, rank, completed optimiser steps, element index): data-parallel ranks draw different masks."""
-
-    def __init__(self, eng, node, prev):
-        super(_DropoutOp, self).__init__(eng, node, prev)
-        self.mask_in_consumer = False
-        import zlib
-        rank = 0
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            rank = torch.distributed.get_rank(eng.group)
-        self.seed = (zlib.crc32(self.name.encode()) ^ 0x5bd1e995 ^ (rank * 0x9E3779B1)) & 0xffffffff
-        kp = node.attrs.get('keep_prob')
-        self.const_keep_prob = float(kp) if isinstance(kp, (int, float)) and not isinstance(kp, bool) else None
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        return s
-
-    def alloc(self, sp, s):
-        sp.shape[self.key] = (s, s)
-        sp.buf[self.key + '/y'] = torch.empty(s, dtype=BF16, device=self.eng.device)
-        sp.buf[self.key + '/dy'] = torch.empty(s, dtype=BF16, device=self.eng.device)
-        sp.buf[self.key + '/dx'] = torch.empty(s, dtype=BF16, device=self.eng.device)
-
-    def _kp(self):
-        if self.const_keep_prob is not None:
-            return self.const_keep_prob
-        return float(self.eng.train_keep_prob) if self.eng.training else 1.0
-
-    def fwd(self, sp):
-        x = self.prev.y(sp)
-        if self.prev.mask_in_consumer:
-            raise NotImplementedError('%s: dropout directly behind a fused-ReLU convolution is not lowered' % self.name)
-        ops.dropout(x, self.y(sp), self.seed, self.eng.step_counter(), self._kp())
-
-    def bwd(self, sp):
-        ops.dropout(self.dy(sp), sp.buf[self.key + '/dx'], self.seed, self.eng.step_counter(), self._kp())
-        self.eng.deliver(sp, self.prev, sp.buf[self.key + '/dx'])
-
-
-class _AvgPoolOp(_PoolOp):
-    """Network.avg_pool (network.py:352-359), window == stride."""
-
-    def fwd(self, sp):
-        (N, W, H, C), _ = sp.shape[self.key]
-        x = self.prev.y(sp)
-        if self.prev.mask_in_consumer:
-            pass            # the ReLU is already applied to the stored activation; only its BACKWARD is deferred to the consumer
-        ops.avgpool(x, self.y(sp), N, W, H, C, self.kw_t, self.kh_f)
-
-    def bwd(self, sp):
-        (N, W, H, C), _ = sp.shape[self.key]
-        pdy, finish = self.eng.grad_dst(sp, self.prev)
-        if pdy is not None:
-            ops.avgpool(self.dy(sp), pdy, N, W, H, C, self.kw_t, self.kh_f, backward=True)
-            if self.prev.mask_in_consumer:
-                ops.eltwise(2, pdy, self.prev.y(sp), pdy)
-            finish()
-
-
-class _ConcatOp(_Op):
-    """Network.concat along the channel axis (network.py:154-158, axis = 3): copies, no arithmetic."""
-
-    def __init__(self, eng, node, prev):
-        super(_ConcatOp, self).__init__(eng, node, prev)
-        if node.attrs.get('axis') not in (3, -1):
-            raise NotImplementedError('%s: concat is lowered along the channel axis only' % self.name)
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        return tuple(s[:-1]) + (sum(self._cin),)
-
-    def alloc(self, sp, s):
-        self._cin = [sp.oshape[p.key][-1] for p in self.inputs]
-        o = self.out_shape(s)
-        sp.shape[self.key] = (s, o)
-        sp.buf[self.key + '/y'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-        sp.buf[self.key + '/dy'] = torch.empty(o, dtype=BF16, device=self.eng.device)
-        for i, c in enumerate(self._cin):
-            sp.buf['%s/part%d' % (self.key, i)] = torch.empty(tuple(s[:-1]) + (c,), dtype=BF16, device=self.eng.device)
-
-    def fwd(self, sp):
-        y, off = self.y(sp), 0
-        for p, c in zip(self.inputs, self._cin):
-            if p.mask_in_consumer:
-                raise NotImplementedError('%s: concat of a fused-ReLU convolution output is not lowered' % self.name)
-            y[..., off:off + c].copy_(p.y(sp))
-            off += c
-
-    def bwd(self, sp):
-        dy, off = self.dy(sp), 0
-        for i, (p, c) in enumerate(zip(self.inputs, self._cin)):
-            part = sp.buf['%s/part%d' % (self.key, i)]
-            part.copy_(dy[..., off:off + c])
-            self.eng.deliver(sp, p, part)
-            off += c
-
-
-class _SoftmaxOp(_Op):
-    """Network.softmax (network.py:441-447) over the last axis of fp32 logits — an inference output (CTC takes unnormalised
-    activations, so nothing differentiates through it in this engine)."""
-
-    def out_shape(self, s):
-        return s
-
-    def alloc(self, sp, s):
-        sp.shape[self.key] = (s, s)
-        sp.buf[self.key + '/y'] = torch.empty(s, dtype=F32, device=self.eng.device)
-
-    def dy(self, sp):
-        return None
-
-    def fwd(self, sp):
-        ops.softmax(self.prev.y(sp), self.y(sp))
-
-    def bwd(self, sp):
-        raise NotImplementedError('%s: softmax is an inference output; the loss takes the unnormalised logits' % self.name)
-
-
-class _BiLstmOp(_Op):
-    """bi_lstm (network.py:97-129: ND = 2 directions of LSTMCell(num_hids // 2)) and one cell of the unidirectional stacked `lstm`
-    (network.py:130-152: ND = 1, LSTMCell(num_hids)), optionally followed by the FC + [N,T] -> [T,N] transpose."""
-
-    def __init__(self, eng, node, prev):
-        super(_BiLstmOp, self).__init__(eng, node, prev)
-        a = node.attrs
-        self.ND = 2 if node.op == 'bi_lstm' else 1
-        self.U, self.C, self.D = a['num_hids'] // self.ND, a['nclasses'], a['din']
-        self.cells = a.get('cells') or [self.name + '/fw', self.name + '/bw']       # variable-name prefix of each direction's LSTMCell
-        self.fc = a.get('fc', self.name)                                            # variable-name prefix of the FC
-        self.with_fc = a.get('with_fc', True)       # False: a hidden layer of a stack, output = [N, T, ND * U]
-        if self.U % 32 or self.D % 32 or self.C % 8:
-            raise NotImplementedError('%s: needs hidden units per direction %% 32 == 0, input features %% 32 == 0, classes %% 8 == 0' % self.name)
-        dev, U, D, C, ND = eng.device, self.U, self.D, self.C, self.ND
-        self.wxT = torch.empty((ND * 4 * U, D), dtype=BF16, device=dev)
-        self.whT = torch.empty((ND, 4 * U, U), dtype=BF16, device=dev)
-        self.bias = torch.empty(ND * 4 * U, dtype=F32, device=dev)
-        self.wfcT = torch.empty((C, ND * U), dtype=BF16, device=dev) if self.with_fc else None
-        self.wcat = torch.empty((D, ND * 4 * U), dtype=BF16, device=dev)
-
-    def dy_needed(self):
-        return True
-
-    def out_shape(self, s):
-        N, T, D = s
-        return (T, N, self.C) if self.with_fc else (N, T, self.ND * self.U)
-
-    def y(self, sp):
-        if self.with_fc:
-            return sp.buf[self.key + '/y']
-        (N, T, _), _ = sp.shape[self.key]
-        return sp.buf[self.key + '/hout'].view(N, T, self.ND * self.U)
-
-    def dy(self, sp):
-        if self.with_fc:
-            return sp.buf[self.key + '/dy']
-        (N, T, _), _ = sp.shape[self.key]
-        return sp.buf[self.key + '/dhout'].view(N, T, self.ND * self.U)
-
-    def _persistent(self, N):
-        return self.ND == 2 and self.eng.persistent_lstm and ops.lstm_seq_supported(N, self.U)
-
-    def alloc(self, sp, s):
-        N, T, D = s
-        U, C, ND, dev = self.U, self.C, self.ND, self.eng.device
-        R = N * T
-        sp.shape[self.key] = (s, self.out_shape(s))
-        b = sp.buf
-        b[self.key + '/xproj'] = torch.empty((R, ND * 4 * U), dtype=F32, device=dev)
-        b[self.key + '/hout'] = torch.zeros((R, ND * U), dtype=BF16, device=dev)
-        b[self.key + '/gates'] = torch.zeros((ND, R, 4 * U), dtype=F32, device=dev)
-        b[self.key + '/cell'] = torch.zeros((ND, R, U), dtype=F32, device=dev)
-        if self.with_fc:
-            b[self.key + '/y'] = torch.empty((T, N, C), dtype=F32, device=dev)      # logits, time-major
-            b[self.key + '/dy'] = torch.empty((R, C), dtype=BF16, device=dev)       # d loss / d logits, [N,T,C]
-            # split partials of the FC weight gradient (ops.gemm_tn_split: added in a fixed order, no float atomics)
-            b[self.key + '/fc_ws'] = torch.empty(ops.gemm_tn_split_workspace(R, ND * U, C), dtype=F32, device=dev)
-        b[self.key + '/dhout'] = torch.empty((R, ND * U), dtype=BF16, device=dev)
-        b[self.key + '/dz'] = torch.zeros((R, ND * 4 * U), dtype=BF16, device=dev)
-        b[self.key + '/dc'] = torch.zeros((ND, N, U), dtype=F32, device=dev)
-        b[self.key + '/hprev'] = torch.empty((ND, R, U), dtype=BF16, device=dev)
-        b[self.key + '/xh'] = torch.empty((ND, R, self.D + U), dtype=BF16, device=dev)
-        if self.ND == 2:
-            words = max(ops.lstm_seq_sync_words(N, U), 64) if self._persistent(N) else 64
-            words = (words + 3) // 4 * 4                   # 16-byte granules: the blocks of a plan become views of ONE arena (ShapePlan)
-            b[self.key + '/sync_f'] = torch.zeros(words, dtype=I32, device=dev)
-            b[self.key + '/sync_b'] = torch.zeros(words, dtype=I32, device=dev)
-            sp.lstm_sync_keys = getattr(sp, 'lstm_sync_keys', ()) + (self.key + '/sync_f', self.key + '/sync_b')
-
-    def shadow_params(self):
-        return [c + '/weights' for c in self.cells] + ([self.fc + '/weights'] if self.with_fc else [])
-
-    def pack_jobs(self):
-        e, U, D, ND = self.eng, self.U, self.D, self.ND
-        jobs = []
-        for d, cell in enumerate(self.cells):
-            w = e.param(cell + '/weights')                  # [D+U, 4U], gate-major columns
-            jobs.append(dict(type=0, R=D, Cc=4 * U, ldin=4 * U, lstm_units=U, src=w[:D], dst=self.wxT[d * 4 * U:(d + 1) * 4 * U]))
-            jobs.append(dict(type=0, R=U, Cc=4 * U, ldin=4 * U, lstm_units=U, src=w[D:], dst=self.whT[d]))
-            jobs.append(dict(type=2, R=D, Cc=4 * U, ldin=4 * U, ldout=ND * 4 * U, src=w, dst=self.wcat[:, d * 4 * U:]))
-        if self.with_fc:
-            wf = e.param(self.fc + '/weights')
-            jobs.append(dict(type=0, R=wf.shape[0], Cc=wf.shape[1], ldin=wf.shape[1], src=wf, dst=self.wfcT))
-        for d, cell in enumerate(self.cells):      # the biases' gate-order permutation rides in the same launch
-            jobs.append(dict(type=4, lstm_units=U, n=4 * U, src=e.param(cell + '/biases'), dst=self.bias[d * 4 * U:(d + 1) * 4 * U]))
-        return jobs
-
-    def fwd(self, sp):
-        e, U, C, ND = self.eng, self.U, self.C, self.ND
-        (N, T, D), _ = sp.shape[self.key]
-        R = N * T
-        b = sp.buf
-        x = self.prev.y(sp).view(R, D)
-        if (self._persistent(N) and ND == 2 and os.environ.get('OCR_LSTM_FUSE_X', '1') != '0' and x.is_contiguous()
-                and ops.lstm_fwd_seq_x_supported(N, U, D)):
-            # the input projection inside the recurrent kernel (its MFMAs run while a step's first poll is under way): no projection GEMM,
-            # no fp32 projection tensor
-            ops.lstm_fwd_seq_x(x, self.wxT, self.bias, self.whT, sp.seq_len, b[self.key + '/hout'], b[self.key + '/gates'],
-                               b[self.key + '/cell'], N, T, U, b[self.key + '/sync_f'], 1.0, prepared=_take_ring(sp, self.key + '/sync_f'))
-        elif self._persistent(N):
-            ops.gemm_nt(x, self.wxT, out=b[self.key + '/xproj'], bias=self.bias)
-            ops.lstm_fwd_seq(b[self.key + '/xproj'], self.whT, sp.seq_len, b[self.key + '/hout'], b[self.key + '/gates'],
-                             b[self.key + '/cell'], N, T, U, b[self.key + '/sync_f'], 1.0, prepared=_take_ring(sp, self.key + '/sync_f'))
-        else:
-            ops.gemm_nt(x, self.wxT, out=b[self.key + '/xproj'], bias=self.bias)
-            for s in range(T):
-                ops.lstm_fwd_step(b[self.key + '/xproj'], self.whT, sp.seq_len, b[self.key + '/hout'],
-                                  b[self.key + '/gates'], b[self.key + '/cell'], N, T, U, s, 1.0, ND)
-        if self.with_fc:
-            ops.gemm_nt(b[self.key + '/hout'], self.wfcT, out=b[self.key + '/y'].view(R, C),
-                        bias=e.param(self.fc + '/biases'), rowswap=(T, N))
-
-    def bwd(self, sp):
-        e, U, C, D, ND = self.eng, self.U, self.C, self.D, self.ND
-        (N, T, _), _ = sp.shape[self.key]
-        R = N * T
-        b = sp.buf
-        hout = b[self.key + '/hout']
-        x = self.prev.y(sp).view(R, D)
-        batched = (D + U) % 128 == 0 and (4 * U) % 128 == 0
-        if self.with_fc:
-            dl = b[self.key + '/dy']
-            # FC: dW += H^T dL, db += colsum dL, dH = dL Wfc^T  (the split contraction is added in a fixed order: the same bits every run)
-            ops.gemm_tn_split(hout, dl, e.grad(self.fc + '/weights'), b[self.key + '/fc_ws'], colsum=e.grad(self.fc + '/biases'))
-            ops.gemm_nt(dl, e.shadow(self.fc + '/weights'), out=b[self.key + '/dhout'])
-        # BPTT, all directions per launch
-        wsh = e.shadow(self.cells[0] + '/weights')
-        stride = e.offset(self.cells[1] + '/weights') - e.offset(self.cells[0] + '/weights') if ND == 2 else 0
-        if self._persistent(N):
-            ops.lstm_bwd_seq(wsh[D:], 4 * U, stride, sp.seq_len, b[self.key + '/dhout'], b[self.key + '/gates'],
-                             b[self.key + '/cell'], b[self.key + '/dz'], N, T, U, b[self.key + '/sync_b'], prepared=_take_ring(sp, self.key + '/sync_b'))
-        else:
-            b[self.key + '/dc'].zero_()
-            for s in range(T - 1, -1, -1):
-                ops.lstm_bwd_step(wsh[D:], 4 * U, stride, sp.seq_len, b[self.key + '/dhout'], b[self.key + '/gates'],
-                                  b[self.key + '/cell'], b[self.key + '/dz'], b[self.key + '/dc'], N, T, U, s, ND)
-        dz = b[self.key + '/dz']
-        gw = [e.grad(cell + '/weights') for cell in self.cells]
-        gb = [e.grad(cell + '/biases') for cell in self.cells]
-        if batched:
-            # dW_d[D+U, 4U] = [x | h_prev,d]^T dz_d for all directions in ONE launch (the TF LSTMCell matrix is applied to
-            # concat([x_t, h_{t-1}]), network.py:104-107): 4 short-K weight-gradient launches become 1
-            xh = b[self.key + '/xh']
-            ops.lstm_xh(x, hout, sp.seq_len, xh, N, T, D, U, ND)
-            scs = (e.offset(self.cells[1] + '/biases') - e.offset(self.cells[0] + '/biases')) if ND == 2 else 0
-            e.tn_push(sp, ops.tn_job(xh, D + U, dz, ND * 4 * U, gw[0], 4 * U, R, D + U, 4 * U, nbatch=ND, strideA=R * (D + U), strideB=4 * U,
-                                     strideOut=stride, colsum=gb[0], strideColsum=scs),
-                      (xh, dz, gw[0], gb[0]),
-                      lambda: ops.gemm_tn_batched(xh, D + U, R * (D + U), dz, ND * 4 * U, 4 * U, gw[0], 4 * U, stride, R, D + U, 4 * U, ND,
-                                                  colsum=gb[0], strideColsum=scs))
-        else:
-            ops.lstm_hprev(hout, sp.seq_len, b[self.key + '/hprev'], N, T, U, ND)
-            for d in range(ND):
-                dzd = dz[:, d * 4 * U:(d + 1) * 4 * U]
-                ops.gemm_tn(x, dzd, gw[d][:D], Mk=R, I=D, J=4 * U, lda=D, ldb=ND * 4 * U, ldo=4 * U, colsum=gb[d])
-                ops.gemm_tn(b[self.key + '/hprev'][d], dzd, gw[d][D:], Mk=R, I=U, J=4 * U, lda=U, ldb=ND * 4 * U, ldo=4 * U)
-        pdy, finish = e.grad_dst(sp, self.prev)
-        if pdy is not None:
-            pmask = self.prev.y(sp).view(R, D) if self.prev.mask_in_consumer else None
-            ops.gemm_nt(dz, self.wcat, out=pdy.view(R, D), mask=pmask)
-            finish()
 
 
 # ====================================================================================================== plan per shape
 class ShapePlan(object):
     """All buffers for one (N, W) input shape plus the captured graphs."""
 
-    def __init__(self, eng, N, W):
+    def _init_fields(self, N, W):
+        """Every host-side field engine code sets on a plan, declared here before any op allocates (no device needed)."""
         self.N, self.W = N, W
         self.buf, self.shape = {}, {}
+        self.scratch = {}
+        self.dy_done = set()
+        self.w9_pending, self.w9_tables = [], {}    # deferred weight-gradient reductions of the running backward pass / their device tables
+        self.w9_pending_bytes = 0                   # ... and the slab bytes they cover (Engine.w9_flush_bytes)
+        self.tn_pending = []                        # plain weight-gradient products waiting for a partner (Engine.tn_push)
+        self.tn_side_open = False                   # a paired launch is running on the side stream (Engine._join_tn)
+        # what the ops' alloc decided for this shape
+        self.fused_pools = set()                    # keys of the max-pools a 3x3 convolution's epilogue writes
+        self.bn_stat_rows = {}                      # conv key -> partial statistics rows its own epilogue writes (0: statistics pass)
+        self.bn_bwd_rows = {}                       # conv key -> partial backward-sum rows its consumer's data gradient writes
+        self.lstm_sync_keys = ()                    # buffer keys of the persistent LSTM launches' hand-off blocks
+        self.lstm_arena, self.lstm_sync = None, ()
+        # state of the last forward pass
+        self.rings_ready, self.rings_armed = set(), False
+        self.graph_fb = self.graph_fwd = self.graph_fb1 = self.graph_fb2 = self.graph_dp = self.graph_step = None
+        self._guard_addrs = None                    # Engine._guard_addrs: None = not built yet, False = no persistent launch
+        self._report = None                         # Engine.report_async's slots
+
+    def __init__(self, eng, N, W):
+        self._init_fields(N, W)
         dev = eng.device
         self.x = torch.zeros((N, W, eng.num_features), dtype=F32, device=dev)
         self.labels = torch.zeros(N * eng.max_label_len, dtype=I32, device=dev)
         self.labels_len = torch.zeros(N, dtype=I32, device=dev)
         self.seq_len = torch.ones(N, dtype=I32, device=dev)
         self.oshape = {'data': (N, W, eng.num_features)}       # output shape per op key (multi-input ops look their inputs up here)
-        self.scratch = {}
-        self.dy_done = set()
-        self.w9_pending, self.w9_tables = [], {}    # deferred weight-gradient reductions of the running backward pass / their device tables
-        self.tn_pending = []                        # plain weight-gradient products waiting for a partner (Engine.tn_push)
         for op in eng.ops:
             s = self.oshape[op.prev.key]
             op.alloc(self, s)
             self.oshape[op.key] = op.out_shape(s)
         # the hand-off blocks of all persistent LSTM launches of a step as views of ONE arena: a training step sets the whole arena to the
         # pattern the kernels start from inside its first kernel (conv1 + pool forward) instead of one fill launch per LSTM launch
-        keys = getattr(self, 'lstm_sync_keys', ())
-        self.lstm_arena = None
+        keys = self.lstm_sync_keys
         if keys:
             self.lstm_arena = torch.zeros(sum(self.buf[k].numel() for k in keys), dtype=I32, device=dev)
             off = 0
@@ -1026,8 +132,6 @@ class ShapePlan(object):
         self.ctc_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         self.decoded = torch.zeros((N, self.T), dtype=I32, device=dev)
         self.decoded_len = torch.zeros(N, dtype=I32, device=dev)
-        self.graph_fb = None
-        self.graph_fwd = None
 
 
 # ====================================================================================================== engine
@@ -1051,33 +155,37 @@ class Engine(object):
         self.use_graphs = use_graphs
         self.persistent_lstm = persistent_lstm
         self.fuse_conv1_pool = fuse_conv1_pool
-        self.fuse_bn_stats = os.environ.get('OCR_FUSE_BN_STATS', '1') != '0'      # batch-norm statistics from the producing convolution's epilogue
-        self.w9_flush_bytes = int(float(os.environ.get('OCR_W9_FLUSH_MB', '80')) * (1 << 20))    # slab bytes after which the pending reductions run (0: one at the end of the body); 80 MB: profiles/r04e
-        self.tn_defer = os.environ.get('OCR_TN_JOBS', '1') != '0'                 # pairs of plain weight-gradient products as one gemm_tn3 launch
-        self.tn_side = os.environ.get('OCR_TN_SIDE', '0') != '0'                  # ... on a side stream beside the main chain's short kernels
+        self.fuse_bn_stats = _switch('OCR_FUSE_BN_STATS')     # batch-norm statistics from the producing convolution's epilogue
+        self.w9_flush_bytes = int(_number('OCR_W9_FLUSH_MB', 80, float) * (1 << 20))    # slab bytes after which the pending reductions run (0: one at the end of the body); 80 MB: profiles/r04e
+        self.tn_defer = _switch('OCR_TN_JOBS')              # pairs of plain weight-gradient products as one gemm_tn3 launch
+        self.tn_side = _switch('OCR_TN_SIDE', False)             # ... on a side stream beside the main chain's short kernels
         self.side_stream = torch.cuda.Stream(device=self.device) if (self.tn_side and torch.device(self.device).type == 'cuda') else None
         self.group = group
         self.world = 1
         self._check_xcd_placement()
-        self.force_allreduce = bool(os.environ.get('OCR_FORCE_ALLREDUCE'))   # exercise the RCCL call on a 1-rank group (tests)
+        self.force_allreduce = bool(_env('OCR_FORCE_ALLREDUCE'))   # exercise the RCCL call on a 1-rank group (tests)
         if group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(group)
-        if os.environ.get('OCR_FAKE_WORLD'):            # single-GPU emulation of identical ranks (tests): see dist.allreduce_sum_
-            self.world = int(os.environ['OCR_FAKE_WORLD'])
+        if _env('OCR_FAKE_WORLD'):                      # single-GPU emulation of identical ranks (tests): see dist.allreduce_sum_
+            self.world = _number('OCR_FAKE_WORLD', None)
             self.force_allreduce = True
-        self.overlap_allreduce = os.environ.get('OCR_OVERLAP_ALLREDUCE', '1') != '0'
+        self.overlap_allreduce = _switch('OCR_OVERLAP_ALLREDUCE')
         # OCR_DP_GRAPH=1 (round 6, opt-in): the WHOLE data-parallel step as ONE hipGraph — the two bucket all-reduces are captured on the communication
         # stream (fork behind the late backward, join in front of the optimiser) instead of being issued by Python between three graphs: no graph
         # boundaries, no host enqueue between them.  Opt-in because a captured RCCL collective cannot be validated on more than one rank here; the
         # engine checks at start-up that a captured collective replays correctly on THIS group and falls back to the three-graph schedule otherwise.
-        self.dp_graph = os.environ.get('OCR_DP_GRAPH', '0') == '1'
+        self.dp_graph = _env('OCR_DP_GRAPH', '0') == '1'
         # OCR_W9_DEFER=0: every 3x3 weight gradient reduces its slabs right behind its own kernel (five reduce launches per step
         # for the CRNN); default: one merged reduction per backward body (bit-identical sums)
-        self.defer_w9 = os.environ.get('OCR_W9_DEFER', '1') != '0'
-        self.w9_defer_max_bytes = int(os.environ.get('OCR_W9_DEFER_MAX_MB', self.W9_DEFER_MAX_BYTES >> 20)) << 20     # only consulted with OCR_W9_FLUSH_MB=0
+        self.defer_w9 = _switch('OCR_W9_DEFER')
+        self.w9_defer_max_bytes = _number('OCR_W9_DEFER_MAX_MB', self.W9_DEFER_MAX_BYTES >> 20) << 20     # only consulted with OCR_W9_FLUSH_MB=0
         self.w9_ws_pool = {}          # layer key -> the largest slab workspace any plan asked for so far (shared by the plans)
         self.comm_stream = torch.cuda.Stream(device=self.device)
         self.dp_host_s = [0.0, 0.0, 0.0, 0.0, 0.0, 0]      # host enqueue seconds of the data-parallel schedule's phases + step count (train_step)
+        self._pack_table = None                          # built by the first refresh_weights
+        self._fault_hook = None                          # fault injection (tests): called with the plan in front of the drop-flag launch
+        self._watch_pending = None                       # the watchdog's outstanding report (_watchdog)
+        self.dropped_reports = 0                         # steps whose update the device dropped, as seen by report_wait
         self._lower(net)                                 # operators first: the parameter layout follows their EXECUTION order
         self._layout(net)
         self._init_params(cfg.RNG_SEED if seed is None else seed)
@@ -1215,7 +323,7 @@ class Engine(object):
         self._pack_njobs, self._pack_blocks = len(jobs), start
 
     def refresh_weights(self):
-        if not hasattr(self, '_pack_table'):
+        if self._pack_table is None:
             self._build_pack_table()
         ops.pack_jobs(self._pack_table, self._pack_njobs, self._pack_blocks)
         for op in self.ops:
@@ -1225,11 +333,10 @@ class Engine(object):
     def _lower(self, net):
         """Topological lowering of the plan reachable from 'logits' (a chain for the shipped models, a DAG with residual
         adds for deeper extractors).  Only data edges count: the second input of bi_lstm is the time_step_len slot."""
-        table = {'conv': _ConvOp, 'fc': _FcOp, 'max_pool': _PoolOp, 'reshape_squeeze': _ViewOp, 'dropout': _DropoutOp, 'bi_lstm': _BiLstmOp, 'lstm': _BiLstmOp,
+        table = {'conv': _conv_op, 'fc': _FcOp, 'max_pool': _PoolOp, 'reshape_squeeze': _ViewOp, 'dropout': _DropoutOp, 'bi_lstm': _BiLstmOp, 'lstm': _BiLstmOp,
                  'add': _AddOp, 'relu': _ReluOp, 'batch_norm': _BatchNormOp, 'avg_pool': _AvgPoolOp, 'concat': _ConcatOp,
                  'softmax': _SoftmaxOp}
         data_op = _InputOp(self)
-        data_op.dy_needed = lambda: False
         built = {}
         self.ops = []
         for nd in execution_order(net.get_output('logits')):
@@ -1252,7 +359,7 @@ class Engine(object):
                 self.ops.append(sub)
                 op = sub
             built[id(nd)] = op
-        if os.environ.get('OCR_FUSE_ADD_RELU', '1') != '0':
+        if _switch('OCR_FUSE_ADD_RELU'):
             # residual blocks: add -> relu (the add's only consumer) as ONE pass forward, and one masked delivery per input backward
             for r in self.ops:
                 a = r.prev
@@ -1270,13 +377,13 @@ class Engine(object):
                         other = a.inputs[1] if a.inputs[0] is p else a.inputs[0]
                         if isinstance(other, _InputOp) or self.ops.index(other) < self.ops.index(p):
                             p.tail_into, a.fwd_by = (a, other), p
-        if os.environ.get('OCR_FUSE_CONV_POOL', '1') != '0':
+        if _switch('OCR_FUSE_CONV_POOL'):
             for b in self.ops:
                 a = b.prev
-                if (isinstance(b, _PoolOp) and isinstance(a, _ConvOp) and a.kind == '3x3' and a.relu and not a.bn and a.biased
+                if (isinstance(b, _PoolOp) and isinstance(a, _Conv3x3Op) and a.relu and not a.bn and a.biased
                         and a.consumers == 1 and (b.kw_t, b.kh_f) in ((1, 2), (2, 2))):
                     a.pool_after = b
-        if os.environ.get('OCR_FUSE_BN_POOL', '1') != '0':
+        if _switch('OCR_FUSE_BN_POOL'):
             # conv + batch norm + ReLU followed by the 1 x 2 max-pool over the feature axis as its only consumer (LSTM_train.py:32-33: conv4_2
             # -> pool): the batch-norm apply pass writes the pooled tensor too, and the batch-norm backward passes route the pool's gradient
             # themselves — no max-pool forward / backward launches, no full-resolution gradient tensor written and re-read twice
@@ -1390,14 +497,13 @@ class Engine(object):
     def _forward(self, sp, training=False):
         self.training = training
         # the flat gradient buffer is cleared by the forward pass's first kernel where that is conv1 + pool (one launch less); else by a fill
-        self._zero_pending = bool(training) and self.grads.numel() % 4 == 0 and os.environ.get('OCR_FUSE_ZERO', '1') != '0'
+        self._zero_pending = bool(training) and self.grads.numel() % 4 == 0 and _switch('OCR_FUSE_ZERO')
         if training and not self._zero_pending:
             self.grads.zero_()
         # likewise the fill of the persistent LSTM launches' hand-off blocks (OCR_FUSE_RINGFILL=0: every launch fills its own); a graph whose
         # first kernel is not conv1 + pool never consumes it and its LSTM launches prepare their blocks themselves
         sp.rings_ready, sp.rings_armed = set(), False
-        self._ones_pending = sp.lstm_arena if (training and getattr(sp, 'lstm_arena', None) is not None
-                                               and os.environ.get('OCR_FUSE_RINGFILL', '1') != '0') else None
+        self._ones_pending = sp.lstm_arena if (training and sp.lstm_arena is not None and _switch('OCR_FUSE_RINGFILL')) else None
         for op in self.ops:
             op.fwd(sp)
         self._ones_pending = None
@@ -1483,7 +589,7 @@ class Engine(object):
                 fallback()
 
     def _join_tn(self, sp):
-        if getattr(sp, 'tn_side_open', False):
+        if sp.tn_side_open:
             torch.cuda.current_stream(self.device).wait_stream(self.side_stream)
             sp.tn_side_open = False
 
@@ -1547,7 +653,7 @@ class Engine(object):
         if not self.use_graphs:
             body1()
             return body2
-        if getattr(sp, 'graph_fb1', None) is None:
+        if sp.graph_fb1 is None:
             body1(); body2()                                    # warm-up outside capture (also uploads the drop flag's address table)
             sp.graph_fb1, sp.graph_fb2 = self._capture(body1), self._capture(body2)
         sp.graph_fb1.replay()
@@ -1558,7 +664,7 @@ class Engine(object):
         the communication stream replayed twice: the buffer must hold world^2 x its start value.  Every rank must agree (an eager MIN all-reduce of
         the verdict), else nobody uses the captured schedule.  gloo (tests: ranks sharing one GPU, staged through the host) is never capturable."""
         import torch.distributed as dist
-        fake = bool(os.environ.get('OCR_FAKE_WORLD'))
+        fake = bool(_env('OCR_FAKE_WORLD'))
         if not fake:
             if not (dist.is_available() and dist.is_initialized()) or dist.get_backend(self.group) != 'nccl':
                 return False
@@ -1617,7 +723,7 @@ class Engine(object):
             torch.cuda.current_stream(self.device).wait_stream(self.comm_stream)
             self._optim_body(None)
 
-        if getattr(sp, 'graph_dp', None) is None:
+        if sp.graph_dp is None:
             # warm-up outside capture: forward + backward only (lazy module loads) — the optimiser mutates state, its first run is the first replay
             self._guard_addrs(sp)                            # (the address table of the drop flag's words is uploaded here, outside the capture)
             self._forward(sp, training=True)
@@ -1638,7 +744,7 @@ class Engine(object):
             self._loss_and_backward(sp, flush=False)      # one merged weight-gradient reduction at the end of the whole backward
             self._backward_early(sp)
 
-        if getattr(sp, 'graph_step', None) is None:
+        if sp.graph_step is None:
             self._guard(sp)                              # (its address table is uploaded here, outside the capture)
             fb()
 
@@ -1708,7 +814,7 @@ class Engine(object):
         ops.optim_init(self.scalars, self.lr)
         self.opt_ready = True
         self.graph_opt = None                            # captured optimiser graphs hold the old slot tensors
-        for sp in getattr(self, 'plans', {}).values():
+        for sp in self.plans.values():
             sp.graph_step = None
             sp.graph_dp = None
 
@@ -1717,7 +823,7 @@ class Engine(object):
         self.lr *= gamma
 
     def _guard_on(self):
-        return os.environ.get('OCR_LSTM_TIMEOUT_GUARD', '1') != '0'
+        return _switch('OCR_LSTM_TIMEOUT_GUARD')
 
     def _dp(self):
         return self.world > 1 or self.force_allreduce
@@ -1726,9 +832,9 @@ class Engine(object):
         """Device addresses of the plan's persistent-LSTM error words (None: the plan has no persistent launch)."""
         if sp is None:
             return None
-        g = getattr(sp, '_guard_addrs', None)
+        g = sp._guard_addrs
         if g is None:
-            words = getattr(sp, 'lstm_sync', ())
+            words = sp.lstm_sync
             g = sp._guard_addrs = (torch.tensor([w[-1:].data_ptr() for w in words], dtype=torch.int64, device=self.device) if words else False)
         return g if g is not False else None
 
@@ -1743,9 +849,8 @@ class Engine(object):
     def _publish_guard(self, sp):
         """Data parallel: one tiny launch at the end of the backward graph that holds the LSTM (both error words are final there) writes this
         rank's 1.0 / 0.0 into the drop flag — the word right behind the late bucket, which the all-reduce that follows sums over the ranks."""
-        hook = getattr(self, '_fault_hook', None)          # fault injection (tests): runs between the LSTM launches and the flag launch
-        if hook is not None:
-            hook(sp)
+        if self._fault_hook is not None:                   # fault injection (tests): runs between the LSTM launches and the flag launch
+            self._fault_hook(sp)
         if self._dp() and self._guard_on():
             ops.guard_flag(self._guard_addrs(sp), self.drop_flag)
 
@@ -1838,7 +943,7 @@ class Engine(object):
     def _watchdog(self):
         """Queue a report of this step into the watchdog's OWN slot and evaluate the one queued 64 steps ago (an event query, no wait):
         a persistent-LSTM time-out raises at most 64 steps late instead of costing a pipeline drain every 64 steps."""
-        pending = getattr(self, '_watch_pending', None)
+        pending = self._watch_pending
         if pending is not None:
             if not pending[1].query():
                 return                            # the 'watch' slot's copy is still in flight: keep that handle, queue nothing over it (ADVICE r3)
@@ -1862,8 +967,8 @@ class Engine(object):
         only this function hands out, a slot is reused only after REPORT_SLOTS - 1 further handles were issued and its previous
         handle was waited for (checked), and the synchronous last_loss() and the watchdog each have a slot of their own."""
         sp = self.last_plan
-        words = getattr(sp, 'lstm_sync', ())
-        ring = getattr(sp, '_report', None)
+        words = sp.lstm_sync
+        ring = sp._report
         if ring is None:
             addrs = torch.tensor([w[-1:].data_ptr() for w in words], dtype=torch.int64, device=self.device) if words else None
             mk = lambda: [torch.zeros(4, dtype=torch.float64, device=self.device), torch.zeros(4, dtype=torch.float64).pin_memory(),
@@ -1898,7 +1003,7 @@ class Engine(object):
             # THIS step's update was dropped on the device (the step's own scalars[72], exported by the report kernel — not a comparison of the global
             # counter: a second report covering the same step, or two dropped steps in a row, used to raise — ADVICE r5): parameters and moments are
             # intact on every rank, training goes on; the reported loss of that step is meaningless.  bits == 0 here means ANOTHER rank timed out.
-            self.dropped_reports = getattr(self, 'dropped_reports', 0) + 1
+            self.dropped_reports += 1
             bad = [i for i in range(len(words)) if (bits >> i) & 1]
             import sys
             sys.stderr.write('[engine] WARNING: %s reported an expired inter-workgroup wait; that step\'s update was dropped on the device%s, parameters intact\n'
