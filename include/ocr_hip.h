@@ -139,6 +139,15 @@ int ocr_conv3x3_relu_pool_codes_bf16(const void* x, const void* wpack, void* y, 
                                      int Cout, const float* bias, int kw, int kh, void* stream);
 int ocr_conv3x3_relu_pool_bf16(const void* x, const void* wpack, void* y, void* pooled, int Nb, int W, int H, int Cin, int Cout,
                                const float* bias, int kw, int kh, void* stream);
+/* The data gradient of a convolution whose producer is such a pool, with the pool's backward pass in its write-out: conv3x3(dy, wdgrad) is
+ * computed at the pooled resolution [Nb, W, H] and ONLY the full-resolution gradient out_full [Nb, W*kw, H*kh, Cout] is stored, routed by the
+ * codes (uint32 [Nb*W*H][Cout / 8]) as ocr_maxpool_bwd_codes routes it (relu_mask: the winner's ReLU bit too) — bit-identical to
+ * ocr_conv3x3_bf16 on an aligned-width conv_k3 kernel + ocr_maxpool_bwd_codes, every byte of out_full written.  Only where
+ * ocr_conv3x3_unpool_supported() != 0 (the aligned-width conv_k3 instances: H in {4, 8}, W % (256 / H) == 0, Nb*W*H % 256 == 0,
+ * Cin % 64 == 0, Cout % 64 == 0); otherwise the call returns 2 and launches nothing. */
+int ocr_conv3x3_unpool_supported(int Nb, int W, int H, int Cin, int Cout, int kw, int kh);
+int ocr_conv3x3_dgrad_unpool_bf16(const void* dy, const void* wdgrad, void* out_full, const void* codes, int Nb, int W, int H, int Cin,
+                                  int Cout, int kw, int kh, int relu_mask, void* stream);
 /* out[I][ldo] (f32) += scale * A^T B, A bf16 [Mk][lda], B bf16 [Mk][ldb]  (weight gradients of matmul layers);
  * colsum (may be NULL): colsum[j] += scale * sum_m B[m][j] — the bias gradient, produced by the same pass */
 int ocr_gemm_tn_bf16(const void* A, long lda, const void* B, long ldb, float* out, long ldo, int Mk, int I, int J,
@@ -265,6 +274,12 @@ int ocr_bn_train_fwd_codes(const void* x, const float* gamma, const float* beta,
                            float eps, int relu, void* workspace, int partial_rows, void* pooled, void* codes, void* stream);
 int ocr_bn_train_bwd_codes(const void* x, const void* codes, const void* dy, void* dx, const float* gamma, const float* save_mean,
                            const float* save_rstd, float* dgamma, float* dbeta, long M, int C, int relu, void* workspace, void* stream);
+/* ... with ocr_conv5_col2im inside the statistics pass: the pooled gradient [M / 2][C] = [Nb][W][HC] is formed from the column matrix `col` of
+ * the full-height convolution behind the pool ([Nb * (W - 1)][2 * HC], M / 2 * C == Nb * W * HC) while the sums are taken, and stored to
+ * dy_pooled_out for the apply pass.  dy_pooled_out, dx, dgamma and dbeta are bit-identical to ocr_conv5_col2im + ocr_bn_train_bwd_codes. */
+int ocr_bn_train_bwd_codes_col(const void* x, const void* codes, const void* col, int Nb, int W, int HC, void* dy_pooled_out, void* dx,
+                               const float* gamma, const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta, long M,
+                               int C, int relu, void* workspace, void* stream);
 /* partial_rows > 0 (not with pooled_dy): dy is ALREADY ReLU-masked and the workspace holds that many rows [rows][2][C] of (sum dz, sum dz *
  * xhat) from the data-gradient kernel that wrote dy — ocr_conv3x3_dgrad_bnbwd_bf16: dx = (mask_y > 0) ? conv3x3(dy, wdgrad) : 0 plus those
  * per-256-pixel-tile sums with xhat = (z - mean) * rstd, rows = ocr_conv3x3_bnbwd_rows(...) (0: shape not covered, use the separate passes).

@@ -82,6 +82,9 @@ _SIGS = {
     "ocr_maxpool_bwd_codes": ([_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P], _I),
     "ocr_bn_train_fwd_codes": ([_P, _P, _P, _P, _P, _L, _I, _F, _I, _P, _I, _P, _P, _P], _I),
     "ocr_bn_train_bwd_codes": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P], _I),
+    "ocr_bn_train_bwd_codes_col": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P], _I),
+    "ocr_conv3x3_unpool_supported": ([_I, _I, _I, _I, _I, _I, _I], _I),
+    "ocr_conv3x3_dgrad_unpool_bf16": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P], _I),
     "ocr_conv3x3_bnbwd_rows": ([_I, _I, _I, _I, _I], _I),
     "ocr_conv3x3_dgrad_bnbwd_bf16": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P], _I),
     "ocr_conv3x3_stats_rows": ([_I, _I, _I, _I, _I, _I], _I),

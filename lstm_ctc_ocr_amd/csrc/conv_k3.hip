@@ -44,6 +44,9 @@ struct K3Args {
     // the partial sums of the batch-norm BACKWARD pass per tile: [M / 256][2][N] = (sum g, sum g * xhat), xhat = (bnz - bn_mean) * bn_rstd
     const bf16_t* bnz; const float* bn_mean; const float* bn_rstd;
     uint32_t* codes;                      // CODES instances (pool_kind 1 / 2): the pool's routing codes [pooled pixels][N / 8]; `out` may then be NULL
+    // UNPOOL instances (pool_kind 5 / 6, a data gradient whose producer is a max-pool): `codes` is READ — the routing codes of the pool in front,
+    // [M pixels][N / 8] — and `out` is the gradient at the pool's INPUT resolution [M * kw * kh][N]; unpool_relu: the winner's ReLU bit masks too
+    int unpool_relu;
 };
 
 #ifdef OCR_EXPERIMENTS
@@ -88,7 +91,10 @@ template <int FM /* 16-pixel fragments per wave: 8 or 4 */, int BN /* channels p
           bool BNB = false /* pool_kind 4 (batch-norm backward sums in the write-out): its own instances — compiled into the common epilogue its
                               48 extra live registers spilled in the 256 x 128 kernels */,
           bool CODES = false /* a fused pool in a training step: the pool write-out also stores the windows' routing codes (pool_code_word), and the
-                                full-resolution rows are not stored when `out` is NULL — its own instances, the common epilogue is unchanged */>
+                                full-resolution rows are not stored when `out` is NULL — its own instances, the common epilogue is unchanged */,
+          int UNPOOL = 0 /* 1 (window 1 x 2) / 2 (2 x 2): the backward pass of the max-pool in front in the write-out — the mirror image of CODES: each
+                            staged row leaves as kw * kh full-resolution rows, routed by the pool's codes (maxpool_bwd_codes_kernel's decision); the
+                            pooled-resolution gradient itself is not stored — its own instances */>
 __device__ __forceinline__ void k3_body(const K3Args& g) {
     constexpr int NW = 8, FN = 4, BM = 256;
     constexpr int WN = BN / 64, WMW = 4 / WN;           // waves along channels / pixels (per K half)
@@ -357,6 +363,42 @@ __device__ __forceinline__ void k3_body(const K3Args& g) {
             }
             __syncthreads();
             constexpr int NIT = 256 * U / 512;
+            if constexpr (UNPOOL != 0) {
+                // Pixel m = m0 + lp of this tile is window m of the pool: element cnt = a * 2 + b of the window (TF scan order, column outer)
+                // is full-resolution row 2m + b (1 x 2) / ((2 col + a) * 2H + 2h + b) (2 x 2; col = m / H over the whole batch, h = m % H) and
+                // receives the stored bf16 bits where the channel's code names it (and, relu_mask, the winner was > 0), else +0: one 4-byte
+                // code load and kw * kh 16-byte stores per (lp, u); every byte of the kw * kh * 256 rows x BN channels is written.
+                constexpr int KW = UNPOOL == 2 ? 2 : 1, KH = 2;
+                const int relu_mask = g.unpool_relu;
+                uint32_t wd[NIT];
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int idx = it * 512 + tid, lp = idx / U, u = idx % U;
+                    wd[it] = g.codes[((long)m0 + lp) * (g.N >> 3) + (n0 >> 3) + u];
+                }
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int idx = it * 512 + tid, lp = idx / U, u = idx % U;
+                    const u32x4 v = *(const u32x4*)(smem + lp * ROWB + ((u ^ (((lp / H) & SWM) << 1)) << 4));
+                    // per channel: the window element that receives the gradient, 8 + index (never matched) where the ReLU mask cuts it
+                    const uint32_t t = (wd[it] & 0x33333333u) | (relu_mask ? ((~wd[it] & 0x44444444u) << 1) : 0u);
+                    const long row0 = KW == 1 ? 2 * ((long)m0 + lp) : ((long)(2 * (col0 + lp / H)) * (2 * H) + 2 * (lp % H));
+                    bf16_t* const dst = g.out + row0 * g.N + n0 + u * 8;
+#pragma unroll
+                    for (int a = 0; a < KW; ++a)
+#pragma unroll
+                        for (int b = 0; b < KH; ++b) {
+                            const uint32_t cnt = (uint32_t)(a * KH + b);
+                            uint32_t keep[4];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j)
+                                keep[j] = ((((t >> (8 * j)) & 15u) == cnt) ? 0x0000ffffu : 0u) | ((((t >> (8 * j + 4)) & 15u) == cnt) ? 0xffff0000u : 0u);
+                            const u32x4 o = {v.x & keep[0], v.y & keep[1], v.z & keep[2], v.w & keep[3]};
+                            *(u32x4*)(dst + ((long)a * (2 * H) + b) * g.N) = o;
+                        }
+                }
+                return;
+            }
             u32x4 val[NIT], mk[NIT], zt[BNB ? NIT : 1];
             float st_s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, st_q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             float bmu[8], brs[8];
@@ -501,6 +543,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <int FM, int BN, int NST, int H, bool SINGLE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_k3c_kernel(K3Args g) { k3_body<FM, BN, NST, H, SINGLE, false, false, true>(g); }
 
+// ... and with the backward pass of the max-pool in front in the write-out (aligned widths, H in {4, 8})
+template <int FM, int BN, int NST, int H, int UNPOOL>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_k3u_kernel(K3Args g) {
+    k3_body<FM, BN, NST, H, false, false, false, false, UNPOOL>(g);
+}
+
+template <int FM, int BN, int NST, int H, int UNPOOL>
+static int run_k3u(const K3Args& g, hipStream_t stream) {
+    constexpr int PS = (256 / H + 2 + 7) / 8 * 8, PPIECES = (H * PS / 8 + 7) / 8 * 8;
+    constexpr int need = NST * BN * 128 + 2 * PPIECES * 1024, xch = 8 * (FM / 2) * 4 * 1024, lds = need > xch ? need : xch;
+    static_assert(lds <= 163840 && 256 * BN * 2 <= lds, "LDS");
+    // what the write-out's index arithmetic rests on: whole tiles, whole channel tiles, tiles inside one image, aligned 16-byte rows
+    if (!g.codes || !g.out || g.flags || g.M <= 0 || g.M % 256 || g.N % BN || g.cH != H || g.cW % (256 / H) || ((size_t)g.out & 15) ||
+        ((size_t)g.codes & 3))
+        return OCR_ERR_INVALID;
+    if (ocr_allow_lds<conv_k3u_kernel<FM, BN, NST, H, UNPOOL>>(lds) != hipSuccess) return OCR_ERR_EXEC;
+    conv_k3u_kernel<FM, BN, NST, H, UNPOOL><<<(g.M / 256) * (g.N / BN), 512, lds, stream>>>(g);
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}
+
 template <int FM, int BN, int NST, int H, bool GENW>
 static int run_k3b(const K3Args& g, hipStream_t stream) {
     constexpr int PS = (256 / H + 2 + 7) / 8 * 8, PPIECES = (H * PS / 8 + 7) / 8 * 8;
@@ -545,9 +608,18 @@ static int run_k3(const K3Args& g, hipStream_t stream) {
 // the instances: tile 'A' = 256 pixels x 128 channels, 'D' = 256 x 64; H and the forms as conv3x3_plan's plan_k3 chose them
 int launch_k3(const ConvPlan& p, const ConvOperands& o, hipStream_t stream) {
     const K3Args g = {(const bf16_t*)o.x, (const bf16_t*)o.wpack, p.M, p.Cout, p.Cin, p.W, p.H, (bf16_t*)o.y, o.bias, (const bf16_t*)o.mask,
-                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.prio, (const bf16_t*)o.bnz, o.bn_mean, o.bn_rstd, (uint32_t*)o.codes};
+                      p.flags, (bf16_t*)o.pool, p.epi_kind, p.prio, (const bf16_t*)o.bnz, o.bn_mean, o.bn_rstd, (uint32_t*)o.codes, o.unpool_relu};
     const int H = p.H;
     const bool A = p.tile == 'A';
+    if (p.epi_kind == CONV_EPI_UNPOOL12 || p.epi_kind == CONV_EPI_UNPOOL22) {
+        if (p.genw || p.single || (H != 4 && H != 8)) return OCR_ERR_INVALID;
+        if (p.epi_kind == CONV_EPI_UNPOOL12) {
+            if (A) return H == 4 ? run_k3u<8, 128, 5, 4, 1>(g, stream) : run_k3u<8, 128, 5, 8, 1>(g, stream);
+            return H == 4 ? run_k3u<4, 64, 4, 4, 1>(g, stream) : run_k3u<4, 64, 4, 8, 1>(g, stream);
+        }
+        if (A) return H == 4 ? run_k3u<8, 128, 5, 4, 2>(g, stream) : run_k3u<8, 128, 5, 8, 2>(g, stream);
+        return H == 4 ? run_k3u<4, 64, 4, 4, 2>(g, stream) : run_k3u<4, 64, 4, 8, 2>(g, stream);
+    }
     if (p.epi_kind == CONV_EPI_BNBWD) {
         if (A) {
             if (p.genw) return H == 4 ? run_k3b<8, 128, 5, 4, true>(g, stream) : run_k3b<8, 128, 5, 8, true>(g, stream);

@@ -18,6 +18,8 @@ enum {   // epilogue forms beyond the flags (ConvPlan::epi_kind; the kernels' po
     CONV_EPI_POOL22 = 2, // fused 2 x 2 max-pool
     CONV_EPI_STATS = 3,  // batch-norm statistics of the output: float partials [M / 256][2][Cout]
     CONV_EPI_BNBWD = 4,  // batch-norm backward sums of a masked data gradient: float partials [M / 256][2][Cout]
+    CONV_EPI_UNPOOL12 = 5,  // a data gradient routed through the 1 x 2 max-pool in front by its codes: y is [2 M][Cout], nothing at [M]
+    CONV_EPI_UNPOOL22 = 6,  // ... through the 2 x 2 max-pool: y is [4 M][Cout]
 };
 
 struct ConvPlan {
@@ -47,6 +49,8 @@ struct ConvOperands {
     const void* bnz; const float* bn_mean; const float* bn_rstd;   // CONV_EPI_BNBWD: the producer's pre-normalisation output and statistics
     void* codes;                                 // CONV_EPI_POOL* on conv_ws / conv_k3 (ocr_conv3x3_pool_codes_supported): the pool's routing codes
                                                  // uint32 [pooled pixels][Cout / 8]; y may then be NULL (no full-resolution output)
+                                                 // CONV_EPI_UNPOOL*: the codes of the pool in front, READ: uint32 [M][Cout / 8]
+    int unpool_relu;                             // CONV_EPI_UNPOOL*: the winner's ReLU bit masks the gradient too
 };
 int launch_halo(const ConvPlan& p, const ConvOperands& o, hipStream_t stream);
 int launch_k2(const ConvPlan& p, const ConvOperands& o, hipStream_t stream);

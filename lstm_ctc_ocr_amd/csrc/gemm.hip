@@ -466,10 +466,27 @@ static bool plan_halo(ConvPlan& p, const ConvKnobs& k) {
     return true;
 }
 
+// The unpool write-outs (a data gradient routed through the max-pool in front): exactly where the aligned-width conv_k3 instances take the
+// shape — the CODES instances' coverage (no general width, no accumulate, no mask), H in {4, 8}: whole 256-pixel tiles inside one image, whole
+// channel tiles.  The tile is the plain data gradient's where that runs an aligned-width conv_k3 (the same instance with another write-out:
+// the same bits); a shape below the tap-reuse kernels' size floor takes A where the channels allow it, else D.
+static void plan_unpool(ConvPlan& p, const ConvKnobs& k) {
+    const int H = p.H;
+    if (!k.k2 || !k.k3 || p.flags || (H != 4 && H != 8) || p.M <= 0 || p.M % 256 || p.W % (256 / H) || (p.Cin & 63) || (p.Cout & 63)) return;
+    if ((long)p.M * p.Cin * 2 >= 0x7fffffffL || (long)p.Cout * 9 * p.Cin * 2 >= 0x7fffffffL) return;      // 32-bit descriptor offsets
+    const ConvPlan plain = conv3x3_plan(p.M, p.W, H, p.Cin, p.Cout, 0, CONV_EPI_PLAIN);
+    p.tile = (plain.family == CONV_K3 && !plain.genw) ? plain.tile : ((p.Cout % 128) ? 'D' : 'A');
+    p.family = CONV_K3; p.genw = false; p.single = false; p.prio = k.k3_prio;
+}
+
 ConvPlan conv3x3_plan(int M, int W, int H, int Cin, int Cout, int flags, int epi_kind) {
     const ConvKnobs& k = conv_knobs();
     ConvPlan p = {};
     p.family = CONV_GEMM; p.M = M; p.W = W; p.H = H; p.Cin = Cin; p.Cout = Cout; p.flags = flags; p.epi_kind = epi_kind;
+    if (epi_kind == CONV_EPI_UNPOOL12 || epi_kind == CONV_EPI_UNPOOL22) {
+        if (g_use_halo) plan_unpool(p, k);
+        return p;
+    }
     if (!g_use_halo || (Cin & 63) || (Cout & 3) || M < 1024 || H > 30) return p;
     if (flags & ~(EPI_BIAS | EPI_RELU | EPI_MASK | EPI_ACCUM)) return p;
     if (epi_kind < CONV_EPI_STATS && plan_ws(p, k)) return p;
@@ -597,6 +614,21 @@ static bool conv3x3_plan_has_codes(const ConvPlan& p) { return p.family == CONV_
 extern "C" int ocr_conv3x3_pool_codes_supported(int Nb, int W, int H, int Cin, int Cout, int kw, int kh) {
     const int kind = conv3x3_pool_kind(kw, kh);
     return kind && conv3x3_plan_has_codes(conv3x3_plan(conv3x3_pixels(Nb, W, H, Cin, Cout), W, H, Cin, Cout, EPI_BIAS | EPI_RELU, kind));
+}
+// The data gradient of the convolution BEHIND such a pool with the pool's backward pass in its write-out: conv3x3(dy, wdgrad) at the pooled
+// resolution [Nb, W, H], stored only as the gradient of the pool's input out_full [Nb, W * kw, H * kh, Cout], routed by the codes of the pool
+// ([Nb * W * H][Cout / 8]) as ocr_maxpool_bwd_codes routes it.  Host-only query first: 0 = not covered, run ocr_conv3x3_bf16 + ocr_maxpool_bwd_codes.
+static int conv3x3_unpool_kind(int kw, int kh) { return (kw == 1 && kh == 2) ? CONV_EPI_UNPOOL12 : ((kw == 2 && kh == 2) ? CONV_EPI_UNPOOL22 : 0); }
+extern "C" int ocr_conv3x3_unpool_supported(int Nb, int W, int H, int Cin, int Cout, int kw, int kh) {
+    const int kind = conv3x3_unpool_kind(kw, kh);
+    return kind && conv3x3_plan(conv3x3_pixels(Nb, W, H, Cin, Cout), W, H, Cin, Cout, 0, kind).family == CONV_K3;
+}
+extern "C" int ocr_conv3x3_dgrad_unpool_bf16(const void* dy, const void* wdgrad, void* out_full, const void* codes, int Nb, int W, int H, int Cin,
+                                             int Cout, int kw, int kh, int relu_mask, void* stream) {
+    if (!dy || !wdgrad || !out_full || !codes || ((size_t)codes & 3) || ((size_t)out_full & 15) || !ocr_conv3x3_unpool_supported(Nb, W, H, Cin, Cout, kw, kh))
+        return OCR_ERR_INVALID;
+    const ConvPlan p = conv3x3_plan(Nb * W * H, W, H, Cin, Cout, 0, conv3x3_unpool_kind(kw, kh));
+    return conv3x3_launch(p, {dy, wdgrad, out_full, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (void*)codes, relu_mask ? 1 : 0}, (hipStream_t)stream);
 }
 extern "C" int ocr_conv3x3_relu_pool_codes_bf16(const void* x, const void* wpack, void* y, void* pooled, void* codes, int Nb, int W, int H,
                                                 int Cin, int Cout, const float* bias, int kw, int kh, void* stream) {

@@ -1054,16 +1054,38 @@ __device__ __forceinline__ void bn_pool_route(const bf16_t* __restrict__ y, cons
 }
 // ... from the codes bn_apply_pool_kernel saved: one word instead of two rows of y.  Bit 0 names the winning row of the pair, bit 2 is the
 // ReLU mask of the winner (a losing row's gradient is zero whatever its own mask says): the decisions bn_pool_route + (y > 0) take on y.
-__device__ __forceinline__ void bn_pool_route_codes(const uint32_t* __restrict__ codes, const bf16_t* __restrict__ dp, long r, int C, int gq,
-                                                    int relu, float (&g)[8]) {
-    const uint32_t word = codes[(r >> 1) * (C >> 3) + gq];
-    unpack8(*(const u32x4*)(dp + (r >> 1) * C + gq * 8), g);
+__device__ __forceinline__ void bn_pool_mask_codes(uint32_t word, long r, int relu, float (&g)[8]) {
     const uint32_t odd = (uint32_t)(r & 1);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const uint32_t code = word >> (4 * c);
         if ((code & 1u) != odd || (relu && !(code & 4u))) g[c] = 0.f;
     }
+}
+__device__ __forceinline__ void bn_pool_route_codes(const uint32_t* __restrict__ codes, const bf16_t* __restrict__ dp, long r, int C, int gq,
+                                                    int relu, float (&g)[8]) {
+    const uint32_t word = codes[(r >> 1) * (C >> 3) + gq];
+    unpack8(*(const u32x4*)(dp + (r >> 1) * C + gq * 8), g);
+    bn_pool_mask_codes(word, r, relu, g);
+}
+// conv5 dgrad overlap-add, eight channels: unit idx of dx [Nb][W][HC / 8] = col[n][w][0:HC] + col[n][w-1][HC:2HC] (col rows exist for w < W-1),
+// the two-term sum (0 + a) + b rounded to bf16 once — conv5_col2im8_kernel's element, and what bn_bwd_stats_col_kernel routes
+__device__ __forceinline__ u32x4 col2im_unit8(const bf16_t* __restrict__ col, unsigned idx, int W, int HC) {
+    const unsigned hc8 = (unsigned)HC >> 3;
+    const unsigned e = (idx % hc8) * 8u, q = idx / hc8;
+    const unsigned w = q % (unsigned)W, n = q / (unsigned)W;
+    float a[8], b[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { a[c] = 0.f; b[c] = 0.f; }
+    const long r0 = ((long)n * (W - 1) + w) * 2L;                    // column row of output position (n, w), first kernel row
+    if ((int)w < W - 1) unpack8(*(const u32x4*)(col + r0 * HC + e), a);
+    if (w > 0) unpack8(*(const u32x4*)(col + (r0 - 1) * HC + e), b);       // (n, w - 1), second kernel row
+    bf16_t o[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = f2bf((0.f + a[c]) + b[c]);
+    u32x4 pk = {(uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16),
+                (uint32_t)o[4] | ((uint32_t)o[5] << 16), (uint32_t)o[6] | ((uint32_t)o[7] << 16)};
+    return pk;
 }
 // backward pass 1: dz = dy * (y > 0) [if relu]; part[block][0][C] = sum dz, part[block][1][C] = sum dz * xhat over the block's rows
 // CODES (both backward passes): the pooled gradient is routed and masked from the forward pass's codes, y is not read — instances of their own:
@@ -1095,6 +1117,41 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const bf16_t* __restr
                     for (int c = 0; c < 8; ++c) if (!(yv[c] > 0.f)) g[c] = 0.f;
                 }
             }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) { s[c] += g[c]; sx[c] = fmaf(g[c], (xv[c] - mu[c]) * rs[c], sx[c]); }
+        }
+    }
+    __shared__ float red[2048];
+    float* dst = part + (long)blockIdx.x * 2 * C;
+    block_channel_reduce<float, true>(s, red, dst, C, groups, rl, gq, rlanes);
+    block_channel_reduce<float, true>(sx, red, dst + C, C, groups, rl, gq, rlanes);
+}
+// bn_bwd_stats_kernel<true> with conv5's col2im inside: the pooled gradient of pair q = r >> 1 is formed from the column matrix (col2im_unit8:
+// two independent 16-byte loads where the plain kernel has one, in an iteration that waits on loads anyway) instead of read from a tensor
+// that a launch of its own wrote and this one re-read; the thread of the pair's EVEN row stores it to dyp for the apply pass.  Rows per block,
+// thread-to-row mapping, accumulation order and the reduction are the plain kernel's: the same partial rows, bit for bit.
+__global__ __launch_bounds__(256) void bn_bwd_stats_col_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ col, int W, int HC,
+                                                               bf16_t* __restrict__ dyp, const float* __restrict__ mean,
+                                                               const float* __restrict__ rstd, float* __restrict__ part,
+                                                               long M, int C, int rows_per_block, int relu,
+                                                               const uint32_t* __restrict__ codes) {
+    const int groups = C >> 3;
+    const int rl = threadIdx.x / groups, gq = threadIdx.x % groups, rlanes = 256 / groups;
+    const long r0 = (long)blockIdx.x * rows_per_block, r1 = min(M, r0 + rows_per_block);
+    float s[8], sx[8], mu[8], rs[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { s[c] = 0.f; sx[c] = 0.f; mu[c] = mean[gq * 8 + c]; rs[c] = rstd[gq * 8 + c]; }
+    if (rl < rlanes) {
+#pragma unroll 4
+        for (long r = r0 + rl; r < r1; r += rlanes) {
+            float xv[8], g[8];
+            unpack8(*(const u32x4*)(x + r * C + gq * 8), xv);
+            const long q = r >> 1;
+            const uint32_t word = codes[q * groups + gq];
+            const u32x4 pk = col2im_unit8(col, (unsigned)(q * groups + gq), W, HC);        // < 2^31 units (checked by the host)
+            if (!(r & 1)) *(u32x4*)(dyp + q * C + gq * 8) = pk;
+            unpack8(pk, g);
+            bn_pool_mask_codes(word, r, relu, g);
 #pragma unroll
             for (int c = 0; c < 8; ++c) { s[c] += g[c]; sx[c] = fmaf(g[c], (xv[c] - mu[c]) * rs[c], sx[c]); }
         }
@@ -1507,22 +1564,9 @@ __global__ void conv5_col2im_kernel(const bf16_t* __restrict__ col, bf16_t* __re
 // the same, eight channels (16 bytes) per thread and 32-bit index arithmetic (the scalar kernel moved two bytes per thread behind two
 // 64-bit divisions: 1.9 TB/s); element-wise the same two-term sum and the same rounding, hence bit-identical
 __global__ __launch_bounds__(256) void conv5_col2im8_kernel(const bf16_t* __restrict__ col, bf16_t* __restrict__ dx, int Nb, int W, int HC) {
-    const unsigned hc8 = (unsigned)HC >> 3;
-    const unsigned total = (unsigned)Nb * W * hc8;                       // < 2^31 (checked by the host)
+    const unsigned total = (unsigned)Nb * W * ((unsigned)HC >> 3);       // < 2^31 (checked by the host)
     for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += gridDim.x * 256u) {
-        const unsigned e = (idx % hc8) * 8u, q = idx / hc8;
-        const unsigned w = q % (unsigned)W, n = q / (unsigned)W;
-        float a[8], b[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) { a[c] = 0.f; b[c] = 0.f; }
-        const long r0 = ((long)n * (W - 1) + w) * 2L;                    // column row of output position (n, w), first kernel row
-        if ((int)w < W - 1) unpack8(*(const u32x4*)(col + r0 * HC + e), a);
-        if (w > 0) unpack8(*(const u32x4*)(col + (r0 - 1) * HC + e), b);       // (n, w - 1), second kernel row
-        bf16_t o[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o[c] = f2bf((0.f + a[c]) + b[c]);
-        u32x4 pk = {(uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16),
-                    (uint32_t)o[4] | ((uint32_t)o[5] << 16), (uint32_t)o[6] | ((uint32_t)o[7] << 16)};
+        const u32x4 pk = col2im_unit8(col, idx, W, HC);
         *(u32x4*)(dx + (long)idx * 8) = pk;
     }
 }
@@ -1957,10 +2001,17 @@ extern "C" int ocr_bn_train_fwd_codes(const void* x, const float* gamma, const f
 // the row pair, bn_pool_route) instead of reading a full-resolution gradient that a max-pool backward pass wrote.
 // partial_rows > 0: `dy` is already the ReLU-masked gradient and the workspace holds that many rows [rows][2][C] of (sum dz, sum dz * xhat) written
 // by the data-gradient kernel that produced it (ocr_conv3x3_dgrad_bnbwd_bf16): no statistics pass, and the apply pass reads neither y nor a mask.
+// cs != NULL (with codes): `dy` is the pooled gradient's buffer, WRITTEN by the statistics pass from the column matrix cs->col (conv5's col2im
+// inside it) and read by the apply pass as usual.
+struct BnColSrc { const void* col; int Nb, W, HC; };
 static int bn_train_bwd_impl(const void* x, const void* y, const void* dy, void* dx, const float* gamma,
                              const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta, long M,
-                             int C, int relu, void* workspace, int pooled_dy, int partial_rows, const void* codes, void* stream_) {
+                             int C, int relu, void* workspace, int pooled_dy, int partial_rows, const void* codes, void* stream_,
+                             const BnColSrc* cs = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
+    if (cs && (!codes || !cs->col || cs->Nb <= 0 || cs->W <= 0 || cs->HC <= 0 || (cs->HC & 7) || ((size_t)cs->col & 15) || ((size_t)dy & 15) ||
+               (long)cs->Nb * cs->W * cs->HC != (M >> 1) * C || (long)cs->Nb * cs->W * (cs->HC >> 3) >= 0x7fffffffL))
+        return OCR_ERR_INVALID;
     if (codes ? (!pooled_dy || ((size_t)codes & 3)) : !y) return OCR_ERR_INVALID;      // the codes stand in for y
     if (!x || !dy || !dx || !gamma || !save_mean || !save_rstd || !dgamma || !dbeta || !workspace || (C & 7) ||
         C > 2048 || M <= 0 || (pooled_dy && (M & 1)) || partial_rows < 0 || (partial_rows && pooled_dy))
@@ -1984,7 +2035,9 @@ static int bn_train_bwd_impl(const void* x, const void* y, const void* dy, void*
     if (partial_rows > nblk) return OCR_ERR_INVALID;                 // the partial rows share the block rows' space in front of `sums`
     if (partial_rows) relu = 0;                                       // premasked
     else {
-        if (codes) bn_bwd_stats_kernel<true><<<nblk, 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, save_mean,
+        if (cs) bn_bwd_stats_col_kernel<<<nblk, 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)cs->col, cs->W, cs->HC, (bf16_t*)dy, save_mean,
+                                                                  save_rstd, part, M, C, rpb, relu, (const uint32_t*)codes);
+        else if (codes) bn_bwd_stats_kernel<true><<<nblk, 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, save_mean,
                                                                     save_rstd, part, M, C, rpb, relu, pooled_dy, (const uint32_t*)codes);
         else bn_bwd_stats_kernel<false><<<nblk, 256, 0, stream>>>((const bf16_t*)x, (const bf16_t*)y, (const bf16_t*)dy, save_mean,
                                                                    save_rstd, part, M, C, rpb, relu, pooled_dy, nullptr);
@@ -2017,6 +2070,15 @@ extern "C" int ocr_bn_train_bwd_codes(const void* x, const void* codes, const vo
                                       const float* save_rstd, float* dgamma, float* dbeta, long M, int C, int relu, void* workspace, void* stream_) {
     if (!codes) return OCR_ERR_INVALID;
     return bn_train_bwd_impl(x, nullptr, dy, dx, gamma, save_mean, save_rstd, dgamma, dbeta, M, C, relu, workspace, 1, 0, codes, stream_);
+}
+// ocr_conv5_col2im(col, dy_pooled_out, Nb, W, HC) + ocr_bn_train_bwd_codes with the overlap-add inside the statistics pass (one launch and one
+// pass over the pooled gradient less): dy_pooled_out, dx, dgamma and dbeta are the same bits.
+extern "C" int ocr_bn_train_bwd_codes_col(const void* x, const void* codes, const void* col, int Nb, int W, int HC, void* dy_pooled_out, void* dx,
+                                          const float* gamma, const float* save_mean, const float* save_rstd, float* dgamma, float* dbeta, long M,
+                                          int C, int relu, void* workspace, void* stream_) {
+    if (!codes || !col) return OCR_ERR_INVALID;
+    const BnColSrc cs = {col, Nb, W, HC};
+    return bn_train_bwd_impl(x, nullptr, dy_pooled_out, dx, gamma, save_mean, save_rstd, dgamma, dbeta, M, C, relu, workspace, 1, 0, codes, stream_, &cs);
 }
 extern "C" int ocr_colsum_bf16(const void* a, float* out, long M, int C, long lda, void* stream) {
     if (!a || !out || (C & 7) || C > 2048 || M <= 0) return OCR_ERR_INVALID;

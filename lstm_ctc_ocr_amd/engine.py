@@ -30,7 +30,7 @@ from .layout import FlatLayout, execution_order, init_host_parameters
 ALIGN = 64               # parameter offsets are multiples of 64 elements (256 B)
 
 # Every environment variable the engine reads (through engine_ops._env / _switch / _number, nowhere else), by the moment it is read.
-# A switch is on unless it is '0' (default in brackets); tests and tools set them between those moments.
+# A switch is on unless it is '0' (default in brackets; a switch whose default is 0 is on when set to anything else); tests and tools set them between those moments.
 #   read once, when the Engine is constructed
 #     OCR_FUSE_BN_STATS [1]      0: batch-norm statistics (and backward sums) by passes of their own, not from the convolutions' write-outs
 #     OCR_W9_FLUSH_MB [80]       slab megabytes after which the pending weight-gradient reductions run; 0: one reduction at the end of the body
@@ -51,6 +51,8 @@ ALIGN = 64               # parameter offsets are multiples of 64 elements (256 B
 #     OCR_CONV1_CODES [1]        0: conv1 + pool's backward recomputes the routing instead of reading saved codes
 #     OCR_CONV1_SLAB [1]         0: conv1 + pool's weight gradient by atomics instead of slabs + the merged reduction
 #     OCR_FUSE_BN_BWD [1]        0: no batch-norm backward sums from the consumer's data-gradient kernel
+#     OCR_FUSE_UNPOOL [1]        0: a max-pool's backward stays a launch of its own behind the data gradient of the 3x3 convolution after it
+#     OCR_FUSE_COL2IM_BN [0]     1: conv5's col2im inside the statistics pass of conv4_2's batch-norm backward (measured: no gain, off by default)
 #     OCR_MAX_WIDTH [320]        widest input the shared slab workspaces are sized for ahead of time
 #   read by every forward pass
 #     OCR_FUSE_ZERO [1]          0: the gradient buffer is cleared by a fill, not by conv1 + pool's launch
@@ -80,6 +82,8 @@ class ShapePlan(object):
         self.fused_pools = set()                    # keys of the max-pools a 3x3 convolution's epilogue writes
         self.bn_stat_rows = {}                      # conv key -> partial statistics rows its own epilogue writes (0: statistics pass)
         self.bn_bwd_rows = {}                       # conv key -> partial backward-sum rows its consumer's data gradient writes
+        self.unpool_pools = set()                   # keys of the max-pools whose backward pass their consumer's data gradient does (no /dy)
+        self.col_bn = {}                            # batch-norm conv key -> (col, Nb, W, HC): its statistics pass does conv5's col2im
         self.lstm_sync_keys = ()                    # buffer keys of the persistent LSTM launches' hand-off blocks
         self.lstm_arena, self.lstm_sync = None, ()
         # state of the last forward pass

@@ -213,6 +213,14 @@ class _ConvOp(_Op):
         dy2 = dy.view(M, self.co)
         if self.bn_pool is not None:            # the pooled gradient, routed by the passes themselves
             dy2 = self.bn_pool.dy(sp).view(M // 2, self.co)
+        colsrc = sp.col_bn.get(self.key)
+        if colsrc is not None:                  # ... and formed by the statistics pass itself from the column matrix of the full-height
+            col, Nb, W, HC = colsrc             # convolution behind the pool (_ConvFullOp._conv_bwd left its col2im out)
+            ops.bn_train_bwd_codes_col(sp.buf[self.key + '/z'].view(M, self.co), codes, col, Nb, W, HC, dy2,
+                                       e.param('%s/%s/gamma' % (self.name, self.name)), sp.buf[self.key + '/mean'],
+                                       sp.buf[self.key + '/rstd'], e.grad('%s/%s/gamma' % (self.name, self.name)),
+                                       e.grad('%s/%s/beta' % (self.name, self.name)), relu, sp.buf[self.key + '/bnws'], out=dz.view(M, self.co))
+            return dz
         ops.bn_train_bwd(sp.buf[self.key + '/z'].view(M, self.co), None if ymask is None else ymask.view(M, self.co), dy2,
                          e.param('%s/%s/gamma' % (self.name, self.name)), sp.buf[self.key + '/mean'],
                          sp.buf[self.key + '/rstd'], e.grad('%s/%s/gamma' % (self.name, self.name)),
@@ -329,6 +337,15 @@ class _Conv3x3Op(_ConvOp):
             # taken by this layer's data-gradient kernel (conv_k3's write-out), where a plane-layout kernel takes the shape
             rows = ops.conv3x3_bnbwd_rows(s[0], s[1], s[2], self.co, self.ci)
             sp.bn_bwd_rows[p.key] = rows if rows * 2 * self.ci * 4 <= sp.buf[p.key + '/bnws'].numel() - 2 * self.ci * 8 else 0
+        if (hasattr(self, 'wdgrad') and _switch('OCR_FUSE_UNPOOL') and isinstance(p, _PoolOp) and p.consumers == 1
+                and getattr(p.prev, 'pool_after', None) is p and p.key in sp.fused_pools and p.prev.key + '/pool_codes' in sp.buf
+                and ops.conv3x3_unpool_supported(s[0], s[1], s[2], self.co, self.ci, p.kw_t, p.kh_f)
+                and ops.conv3x3_kernel_choice(s[0], s[1], s[2], self.co, self.ci, bias=False, relu=False) in ('conv_k3/A', 'conv_k3/D')):
+            # the producer is a max-pool whose own producer saved routing codes, and the plain data gradient runs an aligned-width conv_k3
+            # kernel: that kernel's unpool write-out scatters the gradient straight into the gradient of the pool's INPUT (the same bits as the
+            # pooled gradient + maxpool_bwd_codes) — the pool's backward is a no-op in this plan and its gradient buffer does not exist
+            sp.unpool_pools.add(p.key)
+            del sp.buf[p.key + '/dy']
         # scratch of the slab weight-gradient kernel
         need = ops.conv3x3_wgrad_workspace_bytes(s[0], s[1], s[2], self.ci, self.co)
         have = sp.buf.get('wgrad_ws')
@@ -378,6 +395,13 @@ class _Conv3x3Op(_ConvOp):
                     e._flush_w9(sp)         # (knob OCR_W9_FLUSH_MB: reduce while the slabs are still in the Infinity Cache)
         else:
             ops.conv3x3_wgrad(x, dz, dw, dbias=db, workspace=sp.buf.get('wgrad_ws'))   # bias gradient rides on the same pass
+        if p.key in sp.unpool_pools:            # through the pool in front, by the codes of ITS producer (alloc)
+            pdy, finish = e.grad_dst(sp, p.prev)
+            if pdy is not None:
+                ops.conv3x3_dgrad_unpool(dz, self.wdgrad.view(self.ci, 3, 3, self.co), sp.buf[p.prev.key + '/pool_codes'], p.kw_t, p.kh_f,
+                                         p.prev.mask_in_consumer, out=pdy)
+                finish()
+            return
         # a producer with several consumers (residual graphs): where the halo kernel runs, its epilogue adds to what was already
         # delivered instead of writing a scratch tensor that a second pass adds
         pdy, finish, acc = e.grad_dst_acc(sp, p, ops.conv3x3_accum_supported(o[0], o[1], o[2], self.co, self.ci))
@@ -443,6 +467,14 @@ class _ConvFullOp(_ConvOp):
         super(_ConvFullOp, self).alloc(sp, s)
         N, W, H, C = s
         sp.buf[self.key + '/col'] = torch.empty((N * (W - self.kh + 1), self.kh * H * C), dtype=BF16, device=self.eng.device)
+        p = self.prev
+        bn = getattr(p, 'bn_fused_into', None)
+        if (_switch('OCR_FUSE_COL2IM_BN', False) and isinstance(p, _PoolOp) and bn is not None and p.consumers == 1 and self.kh == 2
+                and not p.mask_in_consumer and bn.key + '/pool_codes' in sp.buf and (H * C) % 8 == 0):
+            # the producer is a pool inside a batch-norm layer that holds routing codes: this layer's data gradient stops at the column
+            # matrix, and that layer's statistics pass forms the pooled gradient from it (no col2im launch; _ConvOp._bn_bwd).  Off by default:
+            # bit-identical, but the statistics pass grows by what the col2im launch took (13.3 -> 19.4 us against 6.0)
+            sp.col_bn[bn.key] = (sp.buf[self.key + '/col'], N, W, H * C)
 
     def _conv_fwd(self, sp, x, out, bias, codes):
         (N, W, H, C), o = sp.shape[self.key]
@@ -466,7 +498,9 @@ class _ConvFullOp(_ConvOp):
             col = sp.buf[self.key + '/col']
             wsh = e.shadow(self.name + '/weights').view(K, self.co)      # [K][co] bf16, k = co contiguous
             ops.gemm_nt(dz2, wsh, out=col, M=M, N=K, K=self.co)
-            ops.conv5_col2im(col, pdy, N, W, H * C)
+            bn = getattr(self.prev, 'bn_fused_into', None)
+            if bn is None or bn.key not in sp.col_bn:       # else: inside that layer's batch-norm statistics pass (alloc recorded col there)
+                ops.conv5_col2im(col, pdy, N, W, H * C)
             finish()
 
 
@@ -536,8 +570,8 @@ class _PoolOp(_Op):
             ops.maxpool_fwd(self.prev.y(sp), self.kw_t, self.kh_f, out=self.y(sp))
 
     def bwd(self, sp):
-        if self.fused_into is not None or self.bn_fused_into is not None:
-            return
+        if self.fused_into is not None or self.bn_fused_into is not None or self.key in sp.unpool_pools:
+            return                  # (unpool_pools: the consumer's data-gradient kernel routed the gradient through this pool)
         pdy, finish = self.eng.grad_dst(sp, self.prev)
         if pdy is not None:
             codes = sp.buf.get(self.prev.key + '/pool_codes') if getattr(self.prev, 'pool_after', None) is self else None

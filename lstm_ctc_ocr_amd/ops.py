@@ -211,6 +211,27 @@ def conv3x3_relu_pool_codes(x, wpack, out, pooled, codes, bias, kw, kh):
     return out, pooled, codes
 
 
+def conv3x3_unpool_supported(Nb, W, H, Cin, Cout, kw, kh):
+    """Whether conv3x3_dgrad_unpool has an instance for this data gradient ((Nb, W, H): the POOLED resolution; host-only query)."""
+    return bool(nat.lib().ocr_conv3x3_unpool_supported(int(Nb), int(W), int(H), int(Cin), int(Cout), int(kw), int(kh)))
+
+
+def conv3x3_dgrad_unpool(dy, wdgrad, codes, kw, kh, relu_mask, out=None):
+    """The data gradient conv3x3(dy, wdgrad) of a convolution behind a max-pool, scattered to the pool's input resolution by the routing codes
+    in the kernel's write-out: bit-identical to maxpool_bwd_codes(codes, conv3x3(dy, wdgrad), kw, kh, relu_mask) where conv3x3 runs an
+    aligned-width conv_k3 kernel; the pooled gradient itself is not stored.  dy bf16 [Nb, W, H, Cin], wdgrad bf16 [Cout, 3, 3, Cin],
+    codes int32 [Nb * W * H, Cout / 8] -> bf16 [Nb, W * kw, H * kh, Cout]."""
+    Nb, W, H, Cin = dy.shape
+    Cout = wdgrad.shape[0]
+    assert codes.dtype == torch.int32 and codes.numel() == Nb * W * H * (Cout // 8), (codes.dtype, tuple(codes.shape))
+    if out is None:
+        out = torch.empty((Nb, W * kw, H * kh, Cout), dtype=BF16, device=dy.device)
+    assert out.numel() == Nb * W * kw * H * kh * Cout
+    call("ocr_conv3x3_dgrad_unpool_bf16", ptr(_dev(dy)), ptr(wdgrad), ptr(out), ptr(codes), Nb, W, H, Cin, Cout, kw, kh, int(relu_mask),
+         _st())
+    return out
+
+
 def gemm_tn(A, B, out, *, Mk=None, I=None, J=None, lda=None, ldb=None, ldo=None, row_group=0, row_skip=0,
             a_row_off=0, scale=1.0, splits=0, colsum=None):
     """out[I][J] (f32) += scale * A^T B;  colsum[J] += scale * column sums of B (bias gradient) when given."""
@@ -474,6 +495,18 @@ def bn_train_bwd(x2d, y2d, dy2d, gamma, save_mean, save_rstd, dgamma, dbeta, rel
     else:
         call("ocr_bn_train_bwd", ptr(_dev(x2d)), ptr(y2d), ptr(dy2d), ptr(out), ptr(gamma), ptr(save_mean), ptr(save_rstd),
              ptr(dgamma), ptr(dbeta), M, C, int(relu), ptr(workspace), _st())
+    return out
+
+
+def bn_train_bwd_codes_col(x2d, codes, col, Nb, W, HC, dy_pooled_out, gamma, save_mean, save_rstd, dgamma, dbeta, relu, workspace, out=None):
+    """conv5_col2im(col, dy_pooled_out, Nb, W, HC) + bn_train_bwd(codes=...) with the overlap-add inside the statistics pass: the pooled
+    gradient is formed from `col` while the sums are taken and stored to dy_pooled_out for the apply pass.  Bit-identical to the pair."""
+    M, C = x2d.shape
+    if out is None: out = torch.empty_like(x2d)
+    assert codes.dtype == torch.int32 and tuple(codes.shape) == (M // 2, C // 8), (codes.dtype, tuple(codes.shape))
+    assert (M // 2) * C == Nb * W * HC and dy_pooled_out.numel() == (M // 2) * C and col.numel() == Nb * (W - 1) * 2 * HC
+    call("ocr_bn_train_bwd_codes_col", ptr(_dev(x2d)), ptr(codes), ptr(col), Nb, W, HC, ptr(dy_pooled_out), ptr(out), ptr(gamma),
+         ptr(save_mean), ptr(save_rstd), ptr(dgamma), ptr(dbeta), M, C, int(relu), ptr(workspace), _st())
     return out
 
 
