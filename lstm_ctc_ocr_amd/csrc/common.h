@@ -47,9 +47,10 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
 __device__ __forceinline__ float bf_lo(uint32_t p) { return __uint_as_float(p << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
 
-// The routing codes of a max-pool window for one 8-channel group, 4 bits per channel (conv1_pool_code's format, nn_ops.hip): index of the FIRST
-// maximum in TF scan order (a * kh + b, a over W) | (maximum > 0) << 2 — from the window's packed bf16 rows, i.e. compared on the values a
-// storing forward pass writes, with the comparisons maxpool_bwd_kernel makes on the stored tensor.
+// The routing codes of a max-pool window for one 8-channel group, 4 bits per channel, channel c at bits 4c .. 4c + 3: bits 0-1 the index of the
+// FIRST maximum in TF scan order (a * kh + b, a over W), bit 2 = (maximum > 0), bit 3 clear — from the window's packed bf16 rows, i.e. compared
+// on the values a storing forward pass writes, with the comparisons maxpool_bwd_kernel makes on the stored tensor.  One format for every
+// producer (conv1.hip, pool.hip, batchnorm.hip, conv_k3.hip, conv_ws.hip) and consumer of codes.
 template <int CNT>
 __device__ __forceinline__ uint32_t pool_code_word(const u32x4 (&rows)[CNT]) {
     uint32_t word = 0;
@@ -96,6 +97,43 @@ __device__ __forceinline__ uint32_t pool_code2_merge(uint32_t c0, uint32_t c1, u
     return ((c0 | (c0 >> 12)) & 0xffu) | (((c1 | (c1 >> 12)) & 0xffu) << 8) | (((c2 | (c2 >> 12)) & 0xffu) << 16) | ((c3 | (c3 >> 12)) << 24);
 }
 
+// Helpers of the streaming kernels that more than one of conv1.hip, pool.hip, batchnorm.hip and stream_ops.hip use.
+// 16 bytes = four packed bf16 pairs -> eight floats
+__device__ __forceinline__ void unpack8(u32x4 p, float* f) {
+    f[0] = bf_lo(p.x); f[1] = bf_hi(p.x); f[2] = bf_lo(p.y); f[3] = bf_hi(p.y);
+    f[4] = bf_lo(p.z); f[5] = bf_hi(p.z); f[6] = bf_lo(p.w); f[7] = bf_hi(p.w);
+}
+// element-wise maximum of packed bf16 pairs (2 / 8 values)
+__device__ __forceinline__ uint32_t max2(uint32_t a, uint32_t b) {
+    // bf16 max is exact: keep the raw bits of the larger half (first operand wins ties)
+    uint32_t lo = (bf_lo(b) > bf_lo(a)) ? (b & 0xffffu) : (a & 0xffffu);
+    uint32_t hi = (bf_hi(b) > bf_hi(a)) ? (b & 0xffff0000u) : (a & 0xffff0000u);
+    return lo | hi;
+}
+__device__ __forceinline__ u32x4 max8(u32x4 a, u32x4 b) {
+    u32x4 r = {max2(a.x, b.x), max2(a.y, b.y), max2(a.z, b.z), max2(a.w, b.w)};
+    return r;
+}
+// conv5 dgrad overlap-add, eight channels: unit idx of dx [Nb][W][HC / 8] = col[n][w][0:HC] + col[n][w-1][HC:2HC] (col rows exist for w < W-1),
+// the two-term sum (0 + a) + b rounded to bf16 once — conv5_col2im8_kernel's element, and what bn_bwd_stats_col_kernel routes
+__device__ __forceinline__ u32x4 col2im_unit8(const bf16_t* __restrict__ col, unsigned idx, int W, int HC) {
+    const unsigned hc8 = (unsigned)HC >> 3;
+    const unsigned e = (idx % hc8) * 8u, q = idx / hc8;
+    const unsigned w = q % (unsigned)W, n = q / (unsigned)W;
+    float a[8], b[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { a[c] = 0.f; b[c] = 0.f; }
+    const long r0 = ((long)n * (W - 1) + w) * 2L;                    // column row of output position (n, w), first kernel row
+    if ((int)w < W - 1) unpack8(*(const u32x4*)(col + r0 * HC + e), a);
+    if (w > 0) unpack8(*(const u32x4*)(col + (r0 - 1) * HC + e), b);       // (n, w - 1), second kernel row
+    bf16_t o[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = f2bf((0.f + a[c]) + b[c]);
+    u32x4 pk = {(uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16),
+                (uint32_t)o[4] | ((uint32_t)o[5] << 16), (uint32_t)o[6] | ((uint32_t)o[7] << 16)};
+    return pk;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -105,6 +143,25 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+// Block-level reduction over the row lanes of a (row lane) x (channel group) thread layout, followed by one
+// atomic (STORE = false) or one plain store (STORE = true: dst is this block's private partial row) per channel.
+// red must hold 256*8 floats.
+template <typename AccT, bool STORE = false>
+__device__ __forceinline__ void block_channel_reduce(const float (&v)[8], float* red, AccT* dst, int C, int groups,
+                                                     int rl, int gq, int rlanes) {
+    __syncthreads();
+    if (rl < rlanes) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) red[rl * C + gq * 8 + c] = v[c];
+    }
+    __syncthreads();
+    for (int ch = threadIdx.x; ch < C; ch += 256) {
+        float t = 0.f;
+        for (int r = 0; r < rlanes; ++r) t += red[r * C + ch];
+        if (STORE) dst[ch] = (AccT)t;
+        else atomicAdd(&dst[ch], (AccT)t);
+    }
 }
 
 // hardware-rate gate non-linearities: v_exp_f32 + v_rcp_f32 (relative error ~1e-6, far below the bf16 storage of h)
@@ -142,6 +199,13 @@ __device__ __forceinline__ void ocr_clk_exit(long long* clk) {
     clk[4] += c - clk[0]; clk[5] += t - clk[1]; clk[6] += 1;
 }
 __host__ __device__ static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of 256 threads for `total` work items of a grid-stride kernel: at least one, at most `cap`
+static inline int grid_for(long total, int cap = 4096) {
+    long b = (total + 255) / 256;
+    if (b > cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
 
 // Lets KERNEL launch with `bytes` of dynamic LDS on the current device (hipFuncSetAttribute MaxDynamicSharedMemorySize): called before
 // every launch, it sets the attribute the first time a device needs that much for this kernel instance and is a load otherwise.

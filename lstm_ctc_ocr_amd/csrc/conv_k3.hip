@@ -38,7 +38,7 @@ struct K3Args {
     int cW, cH;
     bf16_t* out; const float* bias; const bf16_t* mask; int flags;
     bf16_t* pool; int pool_kind;          // as conv_halo: 0 none, 1 feature pairs (1 x 2), 2 2 x 2; 3 = `pool` is float [M / 256][2][N]: per-tile
-                                          // partial sums / sums of squares of the stored bf16 outputs (batch-norm statistics, nn_ops.hip)
+                                          // partial sums / sums of squares of the stored bf16 outputs (batch-norm statistics, batchnorm.hip)
     int prio;                             // MFMA priority of waves 4-7 (the K half that multiplies FIRST in an interval); waves 0-3 use 1
     // pool_kind 4 (a data gradient whose producer is a batch-norm + ReLU layer): the stored values are g = mask(y > 0) * result, and `pool` receives
     // the partial sums of the batch-norm BACKWARD pass per tile: [M / 256][2][N] = (sum g, sum g * xhat), xhat = (bnz - bn_mean) * bn_rstd

@@ -70,7 +70,7 @@ __device__ __forceinline__ u32x4 ws_max8(u32x4 a, u32x4 b) {
     return r;
 }
 
-// The routing codes of a pool window (nn_ops.hip's pool_code_word: 4 bits per channel, index of the FIRST maximum in scan order | (maximum > 0)
+// The routing codes of a pool window (common.h's pool_code_word: 4 bits per channel, index of the FIRST maximum in scan order | (maximum > 0)
 // << 2) in packed 16-bit integer arithmetic, two channels per instruction: the window holds post-ReLU values, i.e. bit patterns 0 .. 0x7FFF that
 // order like the floats (see ws_max2; NaN as there), so "first maximum" is the first element equal to the integer maximum.  ne[e] = min(m -
 // p[e], 1) is 0 where element e is a maximum; the index of the first such e is ne0 * (1 + ne1 * (1 + ne2)) (two elements: ne0).

@@ -594,7 +594,7 @@ struct W9ReduceJob {        // 64 bytes, mirrored by lstm_ctc_ocr_amd/engine.py 
 };
 __global__ __launch_bounds__(256) void wgrad9_reduce_jobs_kernel(const W9ReduceJob* __restrict__ jobs, int njobs) {
     // the block's job = the last one whose block_start <= blockIdx.x, looked up by all threads at once (round 6: the serial scan was one dependent L2
-    // round trip per job in front of every block; nn_ops.hip::pack_jobs_kernel)
+    // round trip per job in front of every block; stream_ops.hip::pack_jobs_kernel)
     __shared__ int jsel[4];
     int j = 0;
     for (int k = threadIdx.x; k < njobs; k += 256)

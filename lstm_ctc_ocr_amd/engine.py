@@ -292,7 +292,7 @@ class Engine(object):
 
     PACK_DTYPE = np.dtype([('type', '<i4'), ('R', '<i4'), ('Cc', '<i4'), ('lstm_units', '<i4'), ('ldin', '<i8'),
                            ('ldout', '<i8'), ('src', '<u8'), ('dst', '<u8'), ('n', '<i8'), ('block_start', '<i4'),
-                           ('nblocks', '<i4')])       # == struct PackJob in csrc/nn_ops.hip (64 bytes)
+                           ('nblocks', '<i4')])       # == struct PackJob in csrc/stream_ops.hip (64 bytes)
 
     def _build_pack_table(self):
         # plain bf16 copies only of the variables some op reads through Engine.shadow (the 3x3 convolution weights — most of the

@@ -1,4 +1,4 @@
-"""fp64 reference of the training batch norm exactly as the device defines it (csrc/nn_ops.hip: bn_stats / bn_finalize / bn_apply /
+"""fp64 reference of the training batch norm exactly as the device defines it (csrc/batchnorm.hip: bn_stats / bn_finalize / bn_apply /
 bn_apply_pool / bn_bwd_stats / bn_bwd_finalize / bn_bwd_apply), plus the input generators and the launch arithmetic that the GPU test
 (tests/test_gpu_bn_train.py) and the CPU test of this module (tests/test_bn_reference.py) share.  Plain module, no GPU.
 
@@ -100,7 +100,7 @@ def backward(x, y, dy, gamma, mean, rstd, relu, pooled_dy=False, dgamma0=None, d
                 abs_dz=dz.abs().sum(0), abs_dzx=(dz * xhat).abs().sum(0))
 
 
-# ================================================================================================ launch arithmetic (nn_ops.hip)
+# ================================================================================================ launch arithmetic (batchnorm.hip)
 def rows_per_block(M, target):
     """bn_rows_per_block_host: rows per block for about `target` blocks, a multiple of 8, at least 8."""
     r = (M + target - 1) // target

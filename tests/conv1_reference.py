@@ -1,5 +1,5 @@
-"""fp64 reference of the first layer exactly as the device defines it (csrc/nn_ops.hip: conv1_fwd_kernel, conv1_wgrad_kernel,
-conv1_pool_fwd_kernel<CODES>, conv1_pool_bwd_kernel<CODES> in its atomics and slab forms), the bounds the device has to meet with their
+"""fp64 reference of the first layer exactly as the device defines it (csrc/conv1.hip: conv1_fwd_kernel, conv1_wgrad_kernel,
+conv1_pool_fwd_tile_kernel<CODES>, conv1_pool_bwd_tile_kernel<CODES> in its atomics and slab forms), the bounds the device has to meet with their
 derivation, and the checker that tests/test_gpu_conv1.py (device) and tests/test_conv1_reference.py (a numpy model, no GPU) share.
 Plain module, numpy only.
 

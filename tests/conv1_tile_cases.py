@@ -1,7 +1,14 @@
-"""Shapes and operands the tile generation of the fused conv1 + pool kernels (csrc/nn_ops.hip: conv1_pool_fwd_tile_kernel,
-conv1_pool_bwd_tile_kernel) is tested at, and the routine that runs its three training launches — shared by tests/test_gpu_conv1_tile.py
-(device; also as a child interpreter's program: `python conv1_tile_cases.py OUT.npz Nb,W,H ...`) and tests/test_conv1_tile_shapes.py (the
-inputs' properties, no GPU).  Plain module.
+"""Shapes and operands the tile generation of the fused conv1 + pool kernels (csrc/conv1.hip: conv1_pool_fwd_tile_kernel,
+conv1_pool_bwd_tile_kernel) is tested at, the routine that runs its three training launches, and what they must give: exact_forward, and the
+slab words of tests/golden/conv1_pool_first_generation.npz — shared by tests/test_gpu_conv1_tile.py (device; also as a child interpreter's
+program: `python conv1_tile_cases.py OUT.npz Nb,W,H ...`) and tests/test_conv1_tile_shapes.py (the inputs' and the fixture's properties, no
+GPU).  Plain module.
+
+The fixture was recorded with this file's program from the first generation of the kernels at commit 29b4ab6 (`make EXPERIMENTS=1`,
+OCR_NATIVE_LIB=<that library> and the knob that selected the first generation there; SHAPES at the default block size, PPB_SHAPE at OCR_CONV1_PPB=32 and 1024), in the same run in
+which that commit's tile kernels passed their bit-equality tests against it and its pooled maps and codes equalled exact_forward.  That
+generation is gone from the library, so the fixture cannot be recorded again: slab sums depend on the order of fp32 additions, and a kernel
+that changes them needs a new argument, not a new recording.
 
 A block owns a run of consecutive pooled pixels and stages the input rows they touch; the shapes are the smallest at which that can go wrong."""
 import os
@@ -20,6 +27,8 @@ SHAPES = (
     (2, 250, 32),       # odd W / 2 = 125
 )
 PPB_SHAPE = (3, 30, 12)           # run again at OCR_CONV1_PPB = 32 and 1024
+PPBS = {256: SHAPES, 32: (PPB_SHAPE,), 1024: (PPB_SHAPE,)}        # what the fixture holds: OCR_CONV1_PPB (256 = default) -> shapes
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv1_pool_first_generation.npz')
 GRID_SEED = {(1, 2, 2): 8}        # one window x 64 channels: the first seed whose window holds a tied positive maximum (the others: seed 1)
 
 
@@ -40,6 +49,23 @@ def tied_positive_share(x, w, b):
     """Share of the (window, channel) pairs whose positive maximum is held by two or more elements (on the reference's bf16 values)."""
     p = cr.Reference(x, w, b).pool()
     return float(((p['pooled'] > 0) & ((p['y'] == p['pooled'][:, :, :, None, :]).sum(3) >= 2)).mean())
+
+
+def exact_forward(shape):
+    """What the training forward must write on grid_operands(shape), from the fp64 reference alone: every product is a multiple of 2^-12 and
+    max |x| sum |w| + max |b| <= 17.5 (17 bits), so the fp32 sums are exact in any order and z is the device's value (tests/
+    test_conv1_tile_shapes.py asserts both).  -> (pooled bf16 bits, uint16 [Nb, W/2, H/2, 64]: the maximum over the window of bf16_rne(relu(z));
+    codes, uint8 of the same shape: first arg-max in scan order | (max > 0) << 2, as cr.unpack_codes unpacks the device's words)."""
+    z, _ = cr.conv(*grid_operands(*shape))
+    y = cr.bf16_rne(cr.act(cr.windows(z), True) + 0.0)          # + 0.0: a -0.0 out of the maximum becomes the device's +0.0
+    pooled = y.max(3)
+    return cr.bf16_bits(pooled), y.argmax(3).astype(np.uint8) | ((pooled > 0).astype(np.uint8) << 2)
+
+
+def fixture_key(ppb, shape, tag):
+    """Key of tests/golden/conv1_pool_first_generation.npz: the slab words (int32 bit patterns) the first generation of the fused kernels
+    wrote on grid_operands(shape) at OCR_CONV1_PPB = ppb, from saved codes (tag 'slab_codes') and from recomputed windows ('slab_recompute')."""
+    return '%d/%dx%dx%d/%s' % ((ppb,) + tuple(shape) + (tag,))
 
 
 def run_train_launches(dev, shape):

@@ -1,4 +1,4 @@
-"""The max-pool routing codes in numpy: what the training forward kernels write (conv1_pool_code / pool_code_word / conv_ws's ws_code_word) and
+"""The max-pool routing codes in numpy: what the training forward kernels write (conv1.hip's conv1_pool_pack / common.h's pool_code_word / conv_ws's ws_code_word) and
 what maxpool_bwd_codes and the batch-norm backward passes read.  Shared by tests/test_pool_codes_model.py (CPU) and
 tests/test_gpu_pool_codes.py.  Plain module, no GPU.
 
@@ -15,7 +15,7 @@ def windows(x, kw, kh):
 
 def pool_codes(x, kw, kh):
     """x: float array [N, W, H, C] holding the bf16 values the storing forward pass writes -> (codes uint32 [windows, C / 8], the 3-bit codes
-    [N, W / kw, H / kh, C]).  conv1_pool_code restated: scan, replace on strictly greater."""
+    [N, W / kw, H / kh, C]).  pool_code_word restated: scan, replace on strictly greater."""
     win = windows(np.asarray(x, dtype=np.float32), kw, kh)
     best, bv = np.zeros(win[..., 0, :].shape, dtype=np.uint32), win[..., 0, :].copy()
     for e in range(1, kw * kh):

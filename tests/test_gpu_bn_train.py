@@ -1,4 +1,4 @@
-"""-m gpu: training-mode batch norm (csrc/nn_ops.hip: bn_stats / bn_finalize / bn_apply / bn_apply_pool / bn_bwd_stats / bn_bwd_finalize /
+"""-m gpu: training-mode batch norm (csrc/batchnorm.hip: bn_stats / bn_finalize / bn_apply / bn_apply_pool / bn_bwd_stats / bn_bwd_finalize /
 bn_bwd_apply) and the per-tile statistics of the convolution epilogues (conv_k3.hip) against the fp64 reference of tests/bn_reference.py.
 
 Shapes: the product tensors (headline, variable width, the ResNet stages) and the edges of the thread layout — groups = C / 8 channel
@@ -164,7 +164,7 @@ def _check_backward(what, ref, dx, dg, db, dg0, db0, gamma, rs, M, chain):
 # ================================================================================================ shapes
 def _tags(M, C):
     """The conditions a shape reaches, from the kernels' own launch arithmetic (bn_reference.layout mirrors bn_rows_per_block_host, groups
-    and rlanes of nn_ops.hip)."""
+    and rlanes of batchnorm.hip)."""
     la = bnr.layout(M, C)
     t = set()
     if la['idle_threads']: t.add('idle')                              # 256 % groups != 0: threads with rl >= rlanes must stay out

@@ -1,4 +1,4 @@
-"""-m gpu: the first layer's kernels (csrc/nn_ops.hip: conv1_fwd, conv1_wgrad, conv1_pool_fwd with and without routing codes, conv1_pool_bwd
+"""-m gpu: the first layer's kernels (csrc/conv1.hip: conv1_fwd, conv1_wgrad, conv1_pool_fwd with and without routing codes, conv1_pool_bwd
 in its atomics and slab forms, with saved codes and with recomputed windows) against the fp64 reference of tests/conv1_reference.py, on
 rendered captchas under the trained taps — where one window in five holds a positive maximum shared by several elements and the first-
 maximum rule decides where the gradient goes — beside the uniform random regime, perturbed taps and constant images.  The bounds, their

@@ -1,14 +1,15 @@
-"""-m gpu: the tile generation of the fused conv1 + pool kernels (csrc/nn_ops.hip: a block stages the input rows of its run of pooled
+"""-m gpu: the tile generation of the fused conv1 + pool kernels (csrc/conv1.hip: a block stages the input rows of its run of pooled
 pixels in LDS once; codes in packed 16-bit integer arithmetic; the backward routes by select-and-multiply) at the shapes of
 tests/conv1_tile_cases.py.
 
-(a) Bit for bit against the first generation, which the experiments flavour of the library keeps behind OCR_CONV1_GEN=1: the pooled map,
-    the routing codes and every slab word of the codes and the recompute instances, on 1/64-grid operands (frequent ties).  The knob and
-    OCR_CONV1_PPB are read once per process, so each variant runs in a child interpreter.
+(a) Bit for bit against the first generation of these kernels (per-lane patch loads, float-compare codes; removed from the library, readable
+    at commit 29b4ab6), on 1/64-grid operands (frequent ties).  Its slab words were recorded from it and are committed as
+    tests/golden/conv1_pool_first_generation.npz; its pooled map and routing codes equalled tc.exact_forward when they were recorded — on
+    these operands every forward sum is exact in fp32, so the fp64 model IS the device result.  OCR_CONV1_PPB is read once per process, so
+    the other block sizes run in a child interpreter.
 (b) Against the fp64 reference of tests/conv1_reference.py, with its bounds (c = 10 / (1 - 10 u) forward; k = ppb / 32 + 6 slab backward),
-    guarded outputs and the two fills — independent of a second library, so a skip in (a) cannot hide a failure.
-tests/test_conv1_tile_shapes.py shows without a GPU that the operands are decisive."""
-import ctypes
+    guarded outputs and the two fills.
+tests/test_conv1_tile_shapes.py shows without a GPU that the operands are decisive and exact, and that the fixture is a valid gradient."""
 import os
 import subprocess
 import sys
@@ -21,7 +22,6 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv1_reference as cr  # noqa: E402
 import conv1_tile_cases as tc  # noqa: E402
 
-from lstm_ctc_ocr_amd import _native as nat  # noqa: E402
 from lstm_ctc_ocr_amd import ops  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -32,57 +32,41 @@ POISON = {BF: (torch.int16, 0x7FC1), F32: (torch.int32, 0x7FC00001), I32: (torch
 _ID = lambda s: '%dx%dx%d' % s
 
 
-def _experiments_library():
-    exp = os.path.join(os.path.dirname(nat.LIB_PATH), 'libocrhip_exp.so')
-    if not os.path.exists(exp):
-        pytest.skip('experiments flavour not built (make -C lstm_ctc_ocr_amd/csrc EXPERIMENTS=1)')
-    try:
-        fn = ctypes.CDLL(exp).ocr_build_id
-        fn.restype = ctypes.c_char_p
-        have = fn().decode()
-    except (OSError, AttributeError):
-        have = None
-    if have != nat.source_build_id(experiments=True):
-        pytest.skip('libocrhip_exp.so is stale (%s, tree %s): rebuild it with make EXPERIMENTS=1' % (have, nat.source_build_id(experiments=True)))
-    return exp
-
-
 def _child(path, shapes, **env):
-    """The launches of tc.run_train_launches in an interpreter of its own -> the arrays it saved."""
+    """The launches of tc.run_train_launches on the product library in an interpreter of its own -> the arrays it saved, by shape."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'tests', 'conv1_tile_cases.py'), str(path)] + ['%d,%d,%d' % s for s in shapes],
-                         env=dict({k: v for k, v in os.environ.items() if k not in ('OCR_NATIVE_LIB', 'OCR_CONV1_GEN')}, **env), capture_output=True, text=True, timeout=300, cwd=ROOT)
+                         env=dict({k: v for k, v in os.environ.items() if k != 'OCR_NATIVE_LIB'}, **env), capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0 and 'TILE_CASES_OK' in out.stdout, out.stdout[-1000:] + out.stderr[-2000:]
-    return dict(np.load(str(path)))
+    d = np.load(str(path))
+    return {s: {k: d['%dx%dx%d/%s' % (s + (k,))] for k in ('pooled', 'codes', 'slab_codes', 'slab_recompute')} for s in shapes}
 
 
-def _assert_same(first, tile, shapes):
+def _assert_same(first, ppb, tile, shapes):
+    """tile[shape] = what tc.run_train_launches returned; first = the fixture."""
     for s in shapes:
-        for k in ('pooled', 'codes', 'slab_codes', 'slab_recompute'):
-            a, b = first['%dx%dx%d/%s' % (s + (k,))], tile['%dx%dx%d/%s' % (s + (k,))]
-            assert a.shape == b.shape and np.array_equal(a, b), (s, k, int((a != b).sum()))
-        key = '%dx%dx%d/' % s
-        assert np.array_equal(tile[key + 'slab_codes'], tile[key + 'slab_recompute'])
+        pooled, codes = tc.exact_forward(s)
+        got = tile[s]
+        assert np.array_equal(got['pooled'].view(np.uint16).reshape(pooled.shape), pooled), (s, 'pooled')
+        assert np.array_equal(cr.unpack_codes(got['codes'], codes.shape), codes), (s, 'codes')
+        for k in ('slab_codes', 'slab_recompute'):
+            a, b = first[tc.fixture_key(ppb, s, k)], got[k]
+            assert a.dtype == b.dtype == np.int32 and a.shape == b.shape and np.array_equal(a, b), (s, k, int((a != b).sum()))
+        assert np.array_equal(got['slab_codes'], got['slab_recompute'])
 
 
-def test_bit_equal_to_first_generation(dev, tmp_path):
-    exp = _experiments_library()
-    first = _child(tmp_path / 'first.npz', tc.SHAPES, OCR_NATIVE_LIB=exp, OCR_CONV1_GEN='1')
-    tile = {}
-    for s in tc.SHAPES:
-        for k, v in tc.run_train_launches(dev, s).items():
-            tile['%dx%dx%d/%s' % (s + (k,))] = v
-    _assert_same(first, tile, tc.SHAPES)
+def test_bit_equal_to_first_generation(dev):
+    assert _ppb() == 256            # the fixture's entries for all of tc.SHAPES are those of the default block size
+    tile = {s: tc.run_train_launches(dev, s) for s in tc.SHAPES}
+    _assert_same(np.load(tc.FIXTURE), 256, tile, tc.SHAPES)
 
 
 @pytest.mark.parametrize("ppb", [32, 1024])
 def test_bit_equal_at_other_block_sizes(dev, tmp_path, ppb):
-    exp = _experiments_library()
     shapes = (tc.PPB_SHAPE,)
-    first = _child(tmp_path / 'first.npz', shapes, OCR_NATIVE_LIB=exp, OCR_CONV1_GEN='1', OCR_CONV1_PPB=str(ppb))
     tile = _child(tmp_path / 'tile.npz', shapes, OCR_CONV1_PPB=str(ppb))
     npix = tc.PPB_SHAPE[0] * (tc.PPB_SHAPE[1] // 2) * (tc.PPB_SHAPE[2] // 2)
-    assert tile['%dx%dx%d/slab_codes' % tc.PPB_SHAPE].shape == (cr.ceil_div(npix, ppb), 640)
-    _assert_same(first, tile, shapes)
+    assert tile[tc.PPB_SHAPE]['slab_codes'].shape == (cr.ceil_div(npix, ppb), 640)
+    _assert_same(np.load(tc.FIXTURE), ppb, tile, shapes)
 
 
 # ------------------------------------------------------------------------------------------------ (b) the fp64 reference

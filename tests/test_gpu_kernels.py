@@ -521,32 +521,6 @@ def test_conv1_pool_fused_equals_unfused(dev, Nb, W, H):
     _conv1_pool_fused_equals_unfused(dev, Nb, W, H)
 
 
-def test_conv1_pool_second_generation_kernels(dev):
-    """OCR_CONV1_V2=1 (measured slightly slower, rejected) exists only in the experiments flavour of the library (`make EXPERIMENTS=1` ->
-    libocrhip_exp.so): the product build neither compiles those kernels nor reads the knob (run against the product library this
-    test re-tested the first generation).  The knob is read once per process, so the variant runs in a child."""
-    import os, subprocess, sys
-    from lstm_ctc_ocr_amd import _native as nat
-    exp = os.path.join(os.path.dirname(nat.LIB_PATH), 'libocrhip_exp.so')
-    if not os.path.exists(exp):
-        pytest.skip('experiments flavour not built (make -C lstm_ctc_ocr_amd/csrc EXPERIMENTS=1)')
-    import ctypes
-    try:
-        fn = ctypes.CDLL(exp).ocr_build_id
-        fn.restype = ctypes.c_char_p
-        have = fn().decode()
-    except (OSError, AttributeError):
-        have = None
-    if have != nat.source_build_id(experiments=True):
-        pytest.skip('libocrhip_exp.so is stale (%s, tree %s): rebuild it with make EXPERIMENTS=1' % (have, nat.source_build_id(experiments=True)))
-    env = dict(os.environ, OCR_CONV1_V2='1', OCR_NATIVE_LIB=exp)
-    code = ("import sys; sys.path.insert(0, %r); import torch; from tests import test_gpu_kernels as t; "
-            "[t._conv1_pool_fused_equals_unfused(torch.device('cuda', 0), *s) for s in ((5, 24, 32), (40, 250, 32), (3, 30, 12))]; print('V2_OK')"
-            % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    out = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and 'V2_OK' in out.stdout, out.stderr[-2000:]
-
-
 @pytest.mark.parametrize("Nb,W,H", [(5, 24, 32), (12, 64, 32)])
 def test_conv1_pool_train_kernels_against_torch(dev, Nb, W, H):
     """The step's own conv1 launches — ocr_conv1_pool_fwd_train (pooled map + routing codes) and ocr_conv1_pool_bwd_slab (per-block partial

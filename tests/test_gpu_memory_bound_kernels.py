@@ -277,7 +277,7 @@ def test_optimizer_dropped_steps_guard_flag_and_step_report(dev, size):
     assert o[1] == 0.0 and o[2] == 0.0 and o[3] == sum(1 << i for i in range(32) if (1 if i == probe else pattern[i]) == 1)
 
 
-# ================================================================================================ pooling (nn_ops.hip, dsl_ops.hip)
+# ================================================================================================ pooling (pool.hip, dsl_ops.hip)
 # ocr_maxpool_fwd / _bwd and ocr_avgpool_bf16: one thread per (output window, 8-channel group), grid capped at 8192 workgroups.
 POOL_CAP = 8192
 POOL_OUT = {"sub_block": (1, 3, 5, 64),         # 120 items
@@ -373,7 +373,7 @@ def test_avgpool_forward_and_backward(dev, regime, kw, kh):
     _assert_bits_equal("avgpool bwd", dx, want)
 
 
-# ================================================================================================ element-wise (nn_ops.hip)
+# ================================================================================================ element-wise (stream_ops.hip)
 ELT_CAP = 4096          # ocr_eltwise_bf16: grid_for(n / 8, 4096), 8 elements per thread
 ELT_N = {"sub_block": 8 * 37, "ragged": 8 * (WG * 9 + RAG), "past_cap": 8 * (2 * ELT_CAP * WG + RAG)}
 
@@ -557,7 +557,7 @@ def test_dropout_mask_is_the_oracles(dev, regime, keep_prob):
                                torch.where(keep, (src.float() * float(inv)).to(BF), zero))
 
 
-# ================================================================================================ casts (nn_ops.hip)
+# ================================================================================================ casts (stream_ops.hip)
 EDGE_BITS = [
     0x00000000, 0x80000000,                          # +-0
     0x00000001, 0x80000001,                          # smallest denormals: round to +-0
@@ -647,7 +647,7 @@ def test_cast2d_and_tnc_to_ntc_edge_values(dev, regime):
     _assert_bf16_rule("tnc_to_ntc_bf16", o, g.permute(1, 0, 2).contiguous())
 
 
-# ================================================================================================ input binding (nn_ops.hip)
+# ================================================================================================ input binding (stream_ops.hip)
 U8_CAP = 4096           # ocr_u8_to_unit_f32 / ocr_bind_batch: grid_for(n / 4), 4 pixels per thread
 U8_N = {"sub_block": 4 * 128, "ragged": 4 * (WG * 3 + RAG), "past_cap": 4 * (2 * U8_CAP * WG + RAG)}
 

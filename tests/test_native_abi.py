@@ -98,7 +98,7 @@ def test_hot_path_has_no_cpu_fallback():
 
 def test_job_table_records_match_the_c_structs():
     """The engine hands three kinds of job tables to one-launch kernels (re-packs, fills, weight-gradient slab reductions); their numpy
-    record layouts must be the C structs' (csrc/nn_ops.hip PackJob, csrc/wgrad9.hip W9ReduceJob; the .hip side
+    record layouts must be the C structs' (csrc/stream_ops.hip PackJob, csrc/wgrad9.hip W9ReduceJob; the .hip side
     static_asserts the sizes), and host-side argument checks of the new entry points reject NULL tables before any launch."""
     from lstm_ctc_ocr_amd.engine import Engine
     off = lambda dt: {n: dt.fields[n][1] for n in dt.names}

@@ -5,7 +5,7 @@
 Beside each time: the bytes the launch has to move, computed from the shapes, per microsecond, and the time those bytes take at RATE (the
 5.8 TB/s adam_update_kernel reaches in profiles/r11_pmc_step_fixed.json).  Hot (back to back) and cold (a 512 MB scrub before every timed launch).
     python tools/conv1_pool_bench.py
-    OCR_NATIVE_LIB=lstm_ctc_ocr_amd/libocrhip_exp.so OCR_CONV1_GEN=1 python tools/conv1_pool_bench.py        # the first generation"""
+    OCR_NATIVE_LIB=lstm_ctc_ocr_amd/libocrhip_exp.so OCR_CONV1_FWD_PPB=64 python tools/conv1_pool_bench.py        # another forward block size"""
 import os
 import sys
 
@@ -45,8 +45,8 @@ def report(name, fn, nbytes):
           % (name, hot, cold, nbytes / 1e6, nbytes / hot, nbytes / cold, nbytes / RATE), flush=True)
 
 
-print('library %s  build %s  OCR_CONV1_GEN=%s OCR_CONV1_LOOKUP=%s OCR_CONV1_FWD_PPB=%s OCR_CONV1_PPB=%s'
-      % (os.path.basename(nat.LIB_PATH), nat.build_id(), *(os.environ.get(k, '-') for k in ('OCR_CONV1_GEN', 'OCR_CONV1_LOOKUP', 'OCR_CONV1_FWD_PPB', 'OCR_CONV1_PPB'))))
+print('library %s  build %s  OCR_CONV1_FWD_PPB=%s OCR_CONV1_PPB=%s'
+      % (os.path.basename(nat.LIB_PATH), nat.build_id(), *(os.environ.get(k, '-') for k in ('OCR_CONV1_FWD_PPB', 'OCR_CONV1_PPB'))))
 for N, W, H in ((64, 256, 32), (64, 320, 32)):
     Co = 64
     npix = N * (W // 2) * (H // 2)
