@@ -210,6 +210,17 @@ int ocr_conv3x3_wgrad_ws_bf16(const void* x, const void* dy, float* dw, float* d
 int ocr_conv3x3_wgrad_defer_bf16(const void* x, const void* dy, float* dw, float* dbias, int Nb, int W, int H, int Cin, int Cout,
                                  void* workspace, size_t workspace_bytes, void* job, int* job_blocks, int* deferred, void* stream);
 int ocr_wgrad9_reduce_jobs(const void* jobs, int njobs, int total_blocks, void* stream);
+/* Two layers' slab kernels in ONE launch, for a layer whose own grid leaves half the chip idle: the first layer's workgroups are dispatched
+ * in front, the second layer's behind them in the same grid.  Each layer is planned exactly as ocr_conv3x3_wgrad_defer_bf16 plans it (same
+ * split count, same slabs: every slab word equals the single launch's), and job0 / job1 receive the two pending reductions.  shape =
+ * {Nb, W, H, Cin, Cout}.  ocr_conv3x3_wgrad_pair_supported (host-only, nothing launched) returns 1 when both shapes take a slab kernel, a
+ * paired instance exists (first: wgrad9_kernel; second: any slab kernel) and the first grid is at most half the CU count; 0 otherwise;
+ * -OCR_STATUS_INVALID for bad arguments.  The launch returns OCR_STATUS_INVALID for a pair that is not supported. */
+int ocr_conv3x3_wgrad_pair_supported(const int* shape_first, const int* shape_second);
+int ocr_conv3x3_wgrad_pair_defer_bf16(const void* x0, const void* dy0, float* dw0, float* dbias0, const int* shape0, void* workspace0,
+                                      size_t workspace_bytes0, const void* x1, const void* dy1, float* dw1, float* dbias1, const int* shape1,
+                                      void* workspace1, size_t workspace_bytes1, void* job0, void* job1, int* job_blocks0, int* job_blocks1,
+                                      void* stream);
 
 /* ---- conv1 (Cin = 1), pooling, batch-norm, reductions, packing (network.py:160-191, 343-350, 176-178) -------- */
 int ocr_conv1_fwd(const float* x, const float* w, const float* bias, void* y, int Nb, int W, int H, int Cout,

@@ -172,6 +172,8 @@ __device__ __forceinline__ float tanhf_(float x) {
     return copysignf(t, x);
 }
 
+int ocr_cu_count();        // CUs of the current device, 256 while none is visible (gemm.hip; host-only plan queries)
+
 // Tuning knobs (tile policies, stage counts, ...): read from the environment only by `make EXPERIMENTS=1` builds — the A/B tools load that
 // library through OCR_NATIVE_LIB; the product library uses the measured defaults.  Kernel-selection knobs that the parity tests force
 // are read by both: OCR_CONV_K2 / OCR_CONV_K3 / OCR_K2_CFG / OCR_CONV_WS / OCR_LSTM_PROTO / OCR_LSTM_ROWS (tests/test_gpu_kernels.py) and

@@ -336,6 +336,17 @@ static const ConvKnobs& conv_knobs() {
     return k;
 }
 
+// CU count of the device: latched only once the query SUCCEEDED (the host-only plan queries of the lowering — possibly no device
+// at all — came first and fixed the 256 fallback for the rest of the process); until then every call asks again
+int ocr_cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0; hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    }
+    return cus > 0 ? cus : 256;                          // no device visible (CPU-only policy tests): the MI355X's count
+}
+
 // conv_ws (weights in registers, workgroups persistent over the pixel tiles) for the short-K layers it covers
 static bool plan_ws(ConvPlan& p, const ConvKnobs& k) {
     if (!k.ws || (p.flags & ~(EPI_BIAS | EPI_RELU | EPI_MASK))) return false;
@@ -347,14 +358,7 @@ static bool plan_ws(ConvPlan& p, const ConvKnobs& k) {
     else if (p.H == 8 && p.Cin == 128) { nc = 16; bm = 128; }
     else return false;
     if (p.W % nc || p.M % bm || (p.epi_kind == CONV_EPI_POOL22 && (p.W & 1))) return false;
-    // CU count of the device: latched only once the query SUCCEEDED (the host-only plan queries of the lowering — possibly no device
-    // at all — came first and fixed the 256 fallback for the rest of the process); until then every call asks again
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    }
-    const int ncu = cus > 0 ? cus : 256;                 // no device visible (CPU-only policy tests): the MI355X's count
+    const int ncu = ocr_cu_count();
     // default policy (measured, profiles/r05e_ws_bench.log): the single-chunk instance (Cin = 64: conv2 forward 40.8 -> 32.3 us) from two tiles
     // per workgroup on; the K-split instances (Cin = 128) are correct but lose to conv_k3 (conv2 data gradient 35 against 28 us, conv3_1 forward
     // 32 against 21: their per-workgroup weight hand-round costs 7-8 us of a 4-tile run) — OCR_CONV_WS=2 runs them for the parity tests

@@ -227,6 +227,11 @@ int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, 
 // the two generations' decisions with the launch cut off (what their dispatchers launch by): kernel code and split count, -1 = not covered
 int tn2_choice(int Mk, int I, int J, int mode, int splits, int nbatch, int* S);
 int wgrad9_choice(int Nb, int W, int H, int Cin, int Cout, int* S);
+// two layers' slab kernels as one launch (wgrad9.hip: the pairing policy and the paired kernels); shapes are {Nb, W, H, Cin, Cout}
+bool wgrad9_pair_ok(int Nb0, int W0, int H0, int Cin0, int Cout0, int Nb1, int W1, int H1, int Cin1, int Cout1);
+int wgrad9_try_dispatch_pair(const void* const x[2], const void* const dy[2], float* const dw[2], float* const dbias[2], const int shape0[5],
+                             const int shape1[5], void* const workspace[2], const size_t ws_bytes[2], hipStream_t stream, void* const job[2],
+                             int* const job_blocks[2]);
 static int g_use_tn2 = 1, g_use_w9 = 1;
 // 2 (default): nine-tap slab kernel (wgrad9.hip) where a workspace is given and the shape is covered, else as 1;
 // 1: LDS-DMA per-tap tiles with fp32 atomics (gemm_tn2.hip); 0: register-staged kernel (this file)
@@ -351,6 +356,35 @@ extern "C" int ocr_conv3x3_wgrad_defer_bf16(const void* x, const void* dy, float
         if (rc >= 0) { if (rc == OCR_OK) *deferred = 1; return rc; }
     }
     return ocr_conv3x3_wgrad_bf16(x, dy, dw, dbias, Nb, W, H, Cin, Cout, 0, stream);
+}
+
+// Can the slab kernels of two layers (shape = {Nb, W, H, Cin, Cout}) run as ONE launch, the first layer's workgroups in front?  Host-only,
+// nothing is launched.  1: yes — both take a slab kernel under the current engine and knobs, a paired instance exists for the two kernels and
+// the first layer's grid fills at most half the CUs (wgrad9.hip: wgrad9_pair_ok is the whole policy); 0: no; -OCR_ERR_INVALID: bad arguments.
+static bool w9_shape_valid(const int* s) { return s && s[0] > 0 && s[1] > 0 && s[2] > 0 && s[3] > 0 && s[4] > 0 && !(s[3] & 7) && !(s[4] & 7); }
+extern "C" int ocr_conv3x3_wgrad_pair_supported(const int* shape_first, const int* shape_second) {
+    if (!w9_shape_valid(shape_first) || !w9_shape_valid(shape_second)) return -OCR_ERR_INVALID;
+    const int *a = shape_first, *b = shape_second;
+    return g_use_w9 && wgrad9_pair_ok(a[0], a[1], a[2], a[3], a[4], b[0], b[1], b[2], b[3], b[4]) ? 1 : 0;
+}
+
+// ocr_conv3x3_wgrad_defer_bf16 for a supported pair of layers: ONE launch runs both slab kernels (each planned exactly as its own launch
+// plans it: same split count, same slabs) and both jobs receive the pending reductions.  OCR_ERR_INVALID where
+// ocr_conv3x3_wgrad_pair_supported says no or a workspace is smaller than ocr_conv3x3_wgrad_workspace_size: nothing runs then.
+extern "C" int ocr_conv3x3_wgrad_pair_defer_bf16(const void* x0, const void* dy0, float* dw0, float* dbias0, const int* shape0, void* workspace0,
+                                                 size_t workspace_bytes0, const void* x1, const void* dy1, float* dw1, float* dbias1,
+                                                 const int* shape1, void* workspace1, size_t workspace_bytes1, void* job0, void* job1,
+                                                 int* job_blocks0, int* job_blocks1, void* stream) {
+    if (!x0 || !dy0 || !dw0 || !x1 || !dy1 || !dw1 || !workspace0 || !workspace1 || !job0 || !job1 || !job_blocks0 || !job_blocks1 ||
+        !w9_shape_valid(shape0) || !w9_shape_valid(shape1))
+        return OCR_ERR_INVALID;
+    if (!g_use_w9) return OCR_ERR_INVALID;
+    const void* const x[2] = {x0, x1}; const void* const dy[2] = {dy0, dy1};
+    float* const dw[2] = {dw0, dw1}; float* const db[2] = {dbias0, dbias1};
+    void* const ws[2] = {workspace0, workspace1}; const size_t wsb[2] = {workspace_bytes0, workspace_bytes1};
+    void* const job[2] = {job0, job1}; int* const nb[2] = {job_blocks0, job_blocks1};
+    const int rc = wgrad9_try_dispatch_pair(x, dy, dw, db, shape0, shape1, ws, wsb, (hipStream_t)stream, job, nb);
+    return rc < 0 ? OCR_ERR_INVALID : rc;
 }
 
 // register-staged 3x3 weight gradient: 128 x 128 tiles (gemm_tn_kernel<1, 4, 4>) from 128 channels on both sides, else 64 x 64 (<1, 2, 2>)

@@ -106,8 +106,8 @@ __device__ __forceinline__ void w9_mfma_tap(f32x4 (&acc)[4], const s16x4& alo, c
 }
 
 // workgroup -> (split, tile) for the three maps of W9Args::map
-__device__ __forceinline__ void w9_block_decode(const W9Args& g, int& split, int& tile) {
-    const int b = blockIdx.x, T = g.T_ci * g.T_co;
+__device__ __forceinline__ void w9_block_decode(const W9Args& g, int b, int& split, int& tile) {
+    const int T = g.T_ci * g.T_co;
     if (g.map == 1) { const int x = b & 7, q = b >> 3; split = (q / T) * 8 + x; tile = q % T; }
     else if (g.map == 2) { const int x = b & 7, q = b >> 3, G = 8 / g.S; split = x / G; tile = (x % G) * (T / G) + q; }
     else { split = b / T; tile = b % T; }
@@ -173,7 +173,10 @@ __device__ __forceinline__ void w9_store_tile(const W9Args& g, unsigned char* sm
     }
 }
 
-__global__ __launch_bounds__(512) void wgrad9_kernel(W9Args g) {
+// The kernels' bodies are device functions of (job, workgroup index within the job): a launch may hold the workgroups of TWO layers
+// (the paired kernels below), so a body never reads blockIdx itself.  The job is taken BY VALUE: through a reference the compiler reschedules
+// the prologue of every single-job kernel; by value the plane kernels stay what they were up to operand order (DESIGN section 9 has the counts).
+__device__ __forceinline__ void wgrad9_body(const W9Args g, int bid) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem;
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(512) void wgrad9_kernel(W9Args g) {
     const int cb = wave & 3, kh = wave >> 2;
     const int H = g.cH, W = g.cW;
     int split, tile;
-    w9_block_decode(g, split, tile);
+    w9_block_decode(g, bid, split, tile);
     const int ti = tile / g.T_co, tj = tile % g.T_co;
     const int ci0 = ti * 64, co0 = tj * 64;
     const int kbeg = split * g.k_per_split;
@@ -336,6 +339,7 @@ __global__ __launch_bounds__(512) void wgrad9_kernel(W9Args g) {
     if (do_cs) w9_cs_store(g, smem, cs, split, co0, tid);
     w9_store_tile(g, smem, acc, split, ci0, co0, cb, kh, lane);
 }
+__global__ __launch_bounds__(512) void wgrad9_kernel(W9Args g) { wgrad9_body(g, blockIdx.x); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // PLANE-LAYOUT form of the kernel above (round 3; same slabs, same reduction, same results up to the summation order inside a step).
@@ -374,7 +378,7 @@ constexpr int w9p_plane(int H, int kh, int kk, int dh, int half) {
     return pl >= 0 && pl < H ? pl : -1;
 }
 template <int H, bool GENW>
-__global__ __launch_bounds__(512) void wgrad9p_kernel(W9Args g) {
+__device__ __forceinline__ void wgrad9p_body(const W9Args g, int bid) {
     constexpr int NC = 128 / H;                         // image columns per step
     constexpr int PS = (NC + 2 + 7) / 8 * 8;            // rows per plane (40 / 24)
     constexpr int XROWS = H * PS, XPIECES = XROWS / 8;  // 160 rows = 20 pieces / 192 rows = 24 pieces; then 128 dY rows = 16 pieces
@@ -388,7 +392,7 @@ __global__ __launch_bounds__(512) void wgrad9p_kernel(W9Args g) {
     const int cb = wave & 3, kh = wave >> 2;
     const int W = g.cW;
     int split, tile;
-    w9_block_decode(g, split, tile);
+    w9_block_decode(g, bid, split, tile);
     const int ti = tile / g.T_co, tj = tile % g.T_co;
     const int ci0 = ti * 64, co0 = tj * 64;
     const int kbeg = split * g.k_per_split;
@@ -540,6 +544,22 @@ __global__ __launch_bounds__(512) void wgrad9p_kernel(W9Args g) {
     W9P_PHASE(4);
 #endif
 }
+template <int H, bool GENW>
+__global__ __launch_bounds__(512) void wgrad9p_kernel(W9Args g) { wgrad9p_body<H, GENW>(g, blockIdx.x); }
+
+// TWO layers' workgroups in ONE grid: blocks [0, nblk_first) are the `first` job's, on wgrad9_kernel's body, the rest the `second` job's on
+// the body <H, GENW> names (H = 16: wgrad9_kernel's body again) — gemm_tn3_kernel(j0, j1, nblk0)'s shape, both jobs as kernel arguments.
+// A layer whose grid fills half the chip or less (conv2: 2 tiles x 64 splits = 128 workgroups of 16 steps on 256 CUs) goes FIRST, so
+// its long, few workgroups start at once; the second layer's start on the CUs it leaves empty and follow on whichever CU frees up.
+// Every workgroup runs exactly the code and the (split, tile) it has in a launch of its own: the slabs are the same words.
+// (An overload of wgrad9p_kernel, not a new name: the profile summaries account the slab kernels by that symbol prefix.)
+template <int H, bool GENW>
+__global__ __launch_bounds__(512) void wgrad9p_kernel(W9Args first, W9Args second, int nblk_first) {
+    const int b = blockIdx.x;
+    if (b < nblk_first) wgrad9_body(first, b);
+    else if constexpr (H == 16) wgrad9_body(second, b - nblk_first);
+    else wgrad9p_body<H, GENW>(second, b - nblk_first);
+}
 
 // dw[i] += sum_s part[s][i];  dbias[co] += sum_s cs_part[s][co] — fixed summation order: deterministic.
 // 256 threads = `rows` thread rows x (256 / rows) float4 columns, rows = S / 8 clamped to [1, 8]: every thread adds up to eight slabs
@@ -662,51 +682,117 @@ int wgrad9_choice(int Nb, int W, int H, int Cin, int Cout, int* S) {
     return k;
 }
 
+// (function-pointer constants: wgrad9p_kernel<H, GENW> names two overloads, the single-job and the paired kernel)
+typedef void (*W9Kernel)(W9Args);
+typedef void (*W9PairKernel)(W9Args, W9Args, int);
+template <int H, bool GENW> constexpr W9Kernel W9P_SINGLE = wgrad9p_kernel<H, GENW>;
+template <int H, bool GENW> constexpr W9PairKernel W9P_PAIR = wgrad9p_kernel<H, GENW>;
+
 template <auto KERNEL>
 static int w9_launch(const W9Args& g, int grid, hipStream_t stream) {
     if (ocr_allow_lds<KERNEL>(W9_LDS) != hipSuccess) return OCR_ERR_EXEC;
     KERNEL<<<grid, 512, W9_LDS, stream>>>(g);
     return OCR_OK;
 }
+template <auto KERNEL>
+static int w9_launch_pair(const W9Args& first, int grid_first, const W9Args& second, int grid_second, hipStream_t stream) {
+    if (ocr_allow_lds<KERNEL>(W9_LDS) != hipSuccess) return OCR_ERR_EXEC;
+    KERNEL<<<grid_first + grid_second, 512, W9_LDS, stream>>>(first, second, grid_first);
+    return OCR_OK;
+}
+
+// plan + kernel arguments of one layer, as every launch form sets them up; -1: shape not covered or workspace too small
+static int w9_setup(const void* x, const void* dy, float* dbias, int Nb, int W, int H, int Cin, int Cout, void* workspace, size_t ws_bytes,
+                    W9Plan* p, W9Args* g) {
+    const int M = Nb * W * H;
+    if (!workspace) return -1;
+    const int kern = w9_choose(M, W, H, Cin, Cout, p);
+    if (kern < 0 || ws_bytes < p->bytes) return -1;
+    *g = W9Args{};
+    g->X = (const bf16_t*)x; g->dY = (const bf16_t*)dy; g->M = M; g->Cin = Cin; g->Cout = Cout; g->cW = W; g->cH = H;
+    g->k_per_split = p->k_per_split; g->S = p->S; g->T_ci = p->T_ci; g->T_co = p->T_co; g->map = p->map;
+    g->part = (float*)workspace;
+    g->cs_part = dbias ? g->part + (size_t)p->S * 9 * Cin * Cout : nullptr;
+    return kern;
+}
+// the reduction that follows a layer's slab kernel: its job record and block count
+static W9ReduceJob w9_reduce_job(const W9Args& g, float* dw, float* dbias, int* blocks) {
+    const long n4 = (long)9 * g.Cin * g.Cout / 4;
+    int rows = g.S / 8;
+    rows = rows < 1 ? 1 : (rows > 8 ? 8 : rows);
+    while (rows & (rows - 1)) rows &= rows - 1;                       // power of two
+    const int cols = 256 / rows;
+    *blocks = (int)((n4 + cols - 1) / cols);
+    return W9ReduceJob{dw, g.part, dbias, g.cs_part, n4, n4, g.S, rows, g.Cout, 0};
+}
 
 // -1: shape not covered or workspace too small (caller falls back to the atomics kernels)
 int wgrad9_try_dispatch(const void* x, const void* dy, float* dw, float* dbias, int Nb, int W, int H, int Cin, int Cout,
                         void* workspace, size_t ws_bytes, hipStream_t stream, void* defer_job, int* defer_blocks) {
     W9Plan p;
-    const int M = Nb * W * H;
-    if (!workspace) return -1;
-    const int kern = w9_choose(M, W, H, Cin, Cout, &p);
-    if (kern < 0 || ws_bytes < p.bytes) return -1;
-    W9Args g = {};
-    g.X = (const bf16_t*)x; g.dY = (const bf16_t*)dy; g.M = M; g.Cin = Cin; g.Cout = Cout; g.cW = W; g.cH = H;
-    g.k_per_split = p.k_per_split; g.S = p.S; g.T_ci = p.T_ci; g.T_co = p.T_co; g.map = p.map;
-    g.part = (float*)workspace;
-    g.cs_part = dbias ? g.part + (size_t)p.S * 9 * Cin * Cout : nullptr;
+    W9Args g;
+    const int kern = w9_setup(x, dy, dbias, Nb, W, H, Cin, Cout, workspace, ws_bytes, &p, &g);
+    if (kern < 0) return -1;
     const int grid = p.S * p.T_ci * p.T_co;
     int rc;
     switch (kern) {
-        case W9K_P4: rc = w9_launch<wgrad9p_kernel<4, false>>(g, grid, stream); break;
-        case W9K_P8: rc = w9_launch<wgrad9p_kernel<8, false>>(g, grid, stream); break;
-        case W9K_P4_ZERO_ROW: rc = w9_launch<wgrad9p_kernel<4, true>>(g, grid, stream); break;
-        case W9K_P8_ZERO_ROW: rc = w9_launch<wgrad9p_kernel<8, true>>(g, grid, stream); break;
+        case W9K_P4: rc = w9_launch<W9P_SINGLE<4, false>>(g, grid, stream); break;
+        case W9K_P8: rc = w9_launch<W9P_SINGLE<8, false>>(g, grid, stream); break;
+        case W9K_P4_ZERO_ROW: rc = w9_launch<W9P_SINGLE<4, true>>(g, grid, stream); break;
+        case W9K_P8_ZERO_ROW: rc = w9_launch<W9P_SINGLE<8, true>>(g, grid, stream); break;
         default: rc = w9_launch<wgrad9_kernel>(g, grid, stream); break;
     }
     if (rc != OCR_OK) return rc;
     OCR_CHECK_LAUNCH();
-    const long n4 = (long)9 * Cin * Cout / 4;
-    int rows = p.S / 8;
-    rows = rows < 1 ? 1 : (rows > 8 ? 8 : rows);
-    while (rows & (rows - 1)) rows &= rows - 1;                       // power of two
-    const int cols = 256 / rows;
-    const int blocks = (int)((n4 + cols - 1) / cols);
+    int blocks;
+    const W9ReduceJob jb = w9_reduce_job(g, dw, dbias, &blocks);
     if (defer_job != nullptr) {                                       // the caller runs this reduction later, with others, in one launch
-        W9ReduceJob jb = {dw, g.part, dbias, g.cs_part, n4, n4, p.S, rows, Cout, 0};
         *(W9ReduceJob*)defer_job = jb;
         *defer_blocks = blocks;
         return OCR_OK;
     }
-    wgrad9_reduce_kernel<<<blocks, 256, 0, stream>>>(dw, g.part, n4, n4, p.S, rows, dbias, g.cs_part, Cout);
+    wgrad9_reduce_kernel<<<blocks, 256, 0, stream>>>(dw, g.part, jb.n4, jb.slab4, jb.S, jb.rows, dbias, g.cs_part, Cout);
     OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}
+
+// ---- two layers in one launch -----------------------------------------------------------------------------------------------------
+// THE pairing policy, stated once (ocr_conv3x3_wgrad_pair_supported and the launch both ask here): both shapes take a slab kernel, the
+// first one wgrad9_kernel (the paired instances are wgrad9 + {wgrad9, the four wgrad9p bodies}), and the first job's grid leaves at least
+// half the chip empty — only then is there room for the second job's workgroups beside it.
+bool wgrad9_pair_ok(int Nb0, int W0, int H0, int Cin0, int Cout0, int Nb1, int W1, int H1, int Cin1, int Cout1) {
+    W9Plan p0, p1;
+    if (w9_choose(Nb0 * W0 * H0, W0, H0, Cin0, Cout0, &p0) != W9K_WGRAD9) return false;
+    if (w9_choose(Nb1 * W1 * H1, W1, H1, Cin1, Cout1, &p1) < 0) return false;
+    return 2 * p0.S * p0.T_ci * p0.T_co <= ocr_cu_count();
+}
+
+// -1: the pair is not supported (policy above) or a workspace is too small: nothing was launched
+int wgrad9_try_dispatch_pair(const void* const x[2], const void* const dy[2], float* const dw[2], float* const dbias[2], const int shape0[5],
+                             const int shape1[5], void* const workspace[2], const size_t ws_bytes[2], hipStream_t stream, void* const job[2],
+                             int* const job_blocks[2]) {
+    if (!wgrad9_pair_ok(shape0[0], shape0[1], shape0[2], shape0[3], shape0[4], shape1[0], shape1[1], shape1[2], shape1[3], shape1[4])) return -1;
+    W9Plan p0, p1;
+    W9Args g0, g1;
+    const int k0 = w9_setup(x[0], dy[0], dbias[0], shape0[0], shape0[1], shape0[2], shape0[3], shape0[4], workspace[0], ws_bytes[0], &p0, &g0);
+    const int k1 = w9_setup(x[1], dy[1], dbias[1], shape1[0], shape1[1], shape1[2], shape1[3], shape1[4], workspace[1], ws_bytes[1], &p1, &g1);
+    if (k0 != W9K_WGRAD9 || k1 < 0) return -1;
+    // Each job keeps the grid, the split count and the workgroup map of its own launch.  The maps place a job's workgroups on the eight XCDs by
+    // (index within the job) & 7 while the hardware deals by blockIdx & 7: where grid0 is no multiple of 8 the second job's map is rotated
+    // against the XCDs — its splits lose their L2 locality, the (split, tile) every workgroup computes and stores stays the same.
+    const int grid0 = p0.S * p0.T_ci * p0.T_co, grid1 = p1.S * p1.T_ci * p1.T_co;
+    int rc;
+    switch (k1) {
+        case W9K_P4: rc = w9_launch_pair<W9P_PAIR<4, false>>(g0, grid0, g1, grid1, stream); break;
+        case W9K_P8: rc = w9_launch_pair<W9P_PAIR<8, false>>(g0, grid0, g1, grid1, stream); break;
+        case W9K_P4_ZERO_ROW: rc = w9_launch_pair<W9P_PAIR<4, true>>(g0, grid0, g1, grid1, stream); break;
+        case W9K_P8_ZERO_ROW: rc = w9_launch_pair<W9P_PAIR<8, true>>(g0, grid0, g1, grid1, stream); break;
+        default: rc = w9_launch_pair<W9P_PAIR<16, false>>(g0, grid0, g1, grid1, stream); break;
+    }
+    if (rc != OCR_OK) return rc;
+    OCR_CHECK_LAUNCH();
+    *(W9ReduceJob*)job[0] = w9_reduce_job(g0, dw[0], dbias[0], job_blocks[0]);
+    *(W9ReduceJob*)job[1] = w9_reduce_job(g1, dw[1], dbias[1], job_blocks[1]);
     return OCR_OK;
 }
 

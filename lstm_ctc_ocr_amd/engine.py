@@ -36,6 +36,7 @@ ALIGN = 64               # parameter offsets are multiples of 64 elements (256 B
 #     OCR_W9_FLUSH_MB [80]       slab megabytes after which the pending weight-gradient reductions run; 0: one reduction at the end of the body
 #     OCR_W9_DEFER [1]           0: every 3x3 weight gradient reduces its slabs right behind its own kernel (shared workspace)
 #     OCR_W9_DEFER_MAX_MB [192]  with OCR_W9_FLUSH_MB=0: total slab megabytes of a plan above which it falls back to the shared workspace
+#     OCR_W9_PAIR [1]            0: every 3x3 weight-gradient slab kernel is a launch of its own, none waits to share a launch with the next layer's
 #     OCR_TN_JOBS [1]            0: every plain weight-gradient product is a launch of its own, no paired gemm_tn3 launch
 #     OCR_TN_SIDE [0]            1: the paired launch runs on a side stream beside the main chain
 #     OCR_OVERLAP_ALLREDUCE [1]  0: data parallel without the split schedule: one all-reduce after the whole backward pass
@@ -77,11 +78,13 @@ class ShapePlan(object):
         self.w9_pending, self.w9_tables = [], {}    # deferred weight-gradient reductions of the running backward pass / their device tables
         self.w9_pending_bytes = 0                   # ... and the slab bytes they cover (Engine.w9_flush_bytes)
         self.tn_pending = []                        # plain weight-gradient products waiting for a partner (Engine.tn_push)
+        self.w9_held = None                         # (key, x, dz, dw, db, workspace): a slab launch waiting for its partner layer (Engine.w9_hold)
         self.tn_side_open = False                   # a paired launch is running on the side stream (Engine._join_tn)
         # what the ops' alloc decided for this shape
         self.fused_pools = set()                    # keys of the max-pools a 3x3 convolution's epilogue writes
         self.bn_stat_rows = {}                      # conv key -> partial statistics rows its own epilogue writes (0: statistics pass)
         self.bn_bwd_rows = {}                       # conv key -> partial backward-sum rows its consumer's data gradient writes
+        self.w9_hold_for = {}                       # conv key A -> conv key B: A's slab kernel waits and runs inside B's launch (_Conv3x3Op._plan_w9_pair)
         self.unpool_pools = set()                   # keys of the max-pools whose backward pass their consumer's data gradient does (no /dy)
         self.col_bn = {}                            # batch-norm conv key -> (col, Nb, W, HC): its statistics pass does conv5's col2im
         self.lstm_sync_keys = ()                    # buffer keys of the persistent LSTM launches' hand-off blocks
@@ -126,6 +129,7 @@ class ShapePlan(object):
             need = max(self.buf[k].numel() for k in own)
             for k in own:
                 del self.buf[k]
+            self.w9_hold_for.clear()                # (no deferred reductions, no paired launches)
             self.buf['wgrad_ws'] = torch.empty(need, dtype=torch.uint8, device=dev)
         self.T, _, self.C = self.oshape[eng.ops[-1].key]
         self.costs = torch.zeros(N, dtype=F32, device=dev)
@@ -182,6 +186,9 @@ class Engine(object):
         # OCR_W9_DEFER=0: every 3x3 weight gradient reduces its slabs right behind its own kernel (five reduce launches per step
         # for the CRNN); default: one merged reduction per backward body (bit-identical sums)
         self.defer_w9 = _switch('OCR_W9_DEFER')
+        # OCR_W9_PAIR=0: no slab kernel waits for the next layer's (default: a layer whose grid fills at most half the chip takes the
+        # previous layer's workgroups into its own launch — same slabs, one launch less; _Conv3x3Op._plan_w9_pair)
+        self.w9_pair = _switch('OCR_W9_PAIR')
         self.w9_defer_max_bytes = _number('OCR_W9_DEFER_MAX_MB', self.W9_DEFER_MAX_BYTES >> 20) << 20     # only consulted with OCR_W9_FLUSH_MB=0
         self.w9_ws_pool = {}          # layer key -> the largest slab workspace any plan asked for so far (shared by the plans)
         self.comm_stream = torch.cuda.Stream(device=self.device)
@@ -519,6 +526,7 @@ class Engine(object):
         sp.dy_done = set()
         sp.w9_pending = []
         sp.tn_pending = []
+        sp.w9_held = None
         logits = self.ops[-1].y(sp)
         # loss = mean over the GLOBAL batch -> d loss / d cost_n = 1 / (N * world)   (network.py:655)
         scale = ocr_dist.loss_scale(sp.N, self.world)
@@ -537,6 +545,7 @@ class Engine(object):
             op.bwd(sp)
         self._flush_tn(sp)                  # (always: the exchange of the late gradients may follow this body)
         self._join_tn(sp)
+        self._release_w9(sp)                # (always, like the plain products: nothing is held across an exchange or a graph boundary)
         if flush:
             self._flush_w9(sp)
 
@@ -560,6 +569,7 @@ class Engine(object):
             op.bwd(sp)
         self._flush_tn(sp)
         self._join_tn(sp)
+        self._release_w9(sp)
         self._flush_w9(sp)
 
     def tn_push(self, sp, job, keep, fallback):
@@ -602,10 +612,34 @@ class Engine(object):
     W9_JOB_DTYPE = np.dtype([('dw', '<u8'), ('part', '<u8'), ('dbias', '<u8'), ('cs_part', '<u8'), ('n4', '<i8'), ('slab4', '<i8'),
                              ('S', '<i4'), ('rows', '<i4'), ('Cout', '<i4'), ('block_start', '<i4')])   # == struct W9ReduceJob (wgrad9.hip)
 
+    def w9_append(self, sp, job, ws):
+        """A slab kernel has been launched: its reduction (job, blocks) joins the pending list, its workspace the flush accounting."""
+        sp.w9_pending.append(job)
+        sp.w9_pending_bytes += ws.numel()
+        if self.w9_flush_bytes and sp.w9_pending_bytes >= self.w9_flush_bytes:
+            self._flush_w9(sp)          # (knob OCR_W9_FLUSH_MB: reduce while the slabs are still in the Infinity Cache)
+
+    def w9_hold(self, sp, key, x, dz, dw, db, ws):
+        """Layer `key`'s slab kernel is not launched now: the next slab layer of this backward body takes its workgroups into its own launch
+        (sp.w9_hold_for; _Conv3x3Op._conv_bwd).  Its reduction is NOT pending yet.  The one hazard of holding is a gradient that reaches the
+        exchange or the optimiser unreduced, so every path that ends a body or builds a reduction table releases first (_release_w9)."""
+        self._release_w9(sp)
+        sp.w9_held = (key, x, dz, dw, db, ws)
+
+    def _release_w9(self, sp):
+        """A held slab kernel whose partner did not come: a launch of its own, exactly the one it would have been without pairing."""
+        held, sp.w9_held = sp.w9_held, None
+        if held is not None:
+            _, x, dz, dw, db, ws = held
+            job, nblk = ops.conv3x3_wgrad_deferred(x, dz, dw, db, ws)
+            if job is not None:
+                self.w9_append(sp, (job, nblk), ws)
+
     def _flush_w9(self, sp):
         """ONE launch for the slab reductions the 3x3 weight-gradient kernels of this backward body left pending (dw += sum of the
         slabs, db += column sums).  The job table depends only on the plan's buffers, so it is uploaded once — on the eager run
         that precedes every capture — and the captured graphs replay the launch with the same device table."""
+        self._release_w9(sp)            # (a held kernel's slabs must exist before a table that may follow it is built)
         pend, sp.w9_pending = sp.w9_pending, []
         sp.w9_pending_bytes = 0
         if not pend:

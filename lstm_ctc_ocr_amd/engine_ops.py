@@ -368,8 +368,33 @@ class _Conv3x3Op(_ConvOp):
                     big = max(need, ops.conv3x3_wgrad_workspace_bytes(s[0], s[1] * scale, s[2], self.ci, self.co))
                 have_ws = pool[self.key] = torch.empty(big, dtype=torch.uint8, device=dev)      # (older plans keep the block their graphs captured)
             sp.buf[self.key + '/w9ws'] = have_ws[:need]
+            if e.w9_pair:
+                self._plan_w9_pair(sp, s)
         elif need and (have is None or have.numel() < need):     # one buffer per plan, shared by all layers (one stream)
             sp.buf['wgrad_ws'] = torch.empty(need, dtype=torch.uint8, device=dev)
+
+    def _plan_w9_pair(self, sp, s):
+        """Should this layer's (A's) slab kernel wait for layer B's and run inside B's launch?  B = the next op in BACKWARD order that runs a slab
+        kernel (= the nearest earlier 3x3 layer with slabs of its own: with deferred reductions every slab layer has them), in the same backward
+        body (same side of Engine.split_op: nothing is held across the exchange between the bodies), not itself waiting for a third layer, and
+        ocr_conv3x3_wgrad_pair_supported(B, A) — the library's policy: B alone leaves at least half the chip empty.
+        Why A's operands survive the wait (A's backward .. B's backward): x is a forward activation (prev.y) and dz is A's own gradient
+        buffer (key/dy, or key/dz behind a batch norm), complete before A's backward runs — every consumer of A comes earlier in backward
+        order, in residual graphs too, where grad_dst / grad_dst_acc deliver into the PRODUCER's dy or a scratch tensor, never into a
+        consumer's.  Backward ops write gradient buffers of ops in front of them, weight gradients and workspaces; none writes a y, and each
+        key owns its tensors (no aliasing between keys), so no op between A and B touches either operand."""
+        e = self.eng
+        i = e.ops.index(self)
+        for j in range(i - 1, -1, -1):
+            b = e.ops[j]
+            if isinstance(b, _Conv1Op) and b.key + '/slab' in sp.buf:
+                return          # (reduce jobs of its own in between: the order of the pending list would change)
+            if isinstance(b, _Conv3x3Op) and b.key + '/w9ws' in sp.buf:
+                bs = sp.shape[b.key][0]
+                if ((i >= e.split_op) == (j >= e.split_op) and b.key not in sp.w9_hold_for
+                        and ops.conv3x3_wgrad_pair_supported((bs[0], bs[1], bs[2], b.ci, b.co), (s[0], s[1], s[2], self.ci, self.co))):
+                    sp.w9_hold_for[self.key] = b.key
+                return
 
     def _conv_fwd(self, sp, x, out, bias, codes):
         w, p = self.wpack.view(self.co, 3, 3, self.ci), self.pool_after
@@ -386,13 +411,21 @@ class _Conv3x3Op(_ConvOp):
     def _conv_bwd(self, sp, x, dz, dw, db):
         e, o, p = self.eng, sp.shape[self.key][1], self.prev
         own_ws = sp.buf.get(self.key + '/w9ws')
-        if own_ws is not None:      # slab kernel now, the reduction with the other layers' at the end of the pass
+        held = sp.w9_held
+        if own_ws is not None and self.key in sp.w9_hold_for:
+            e.w9_hold(sp, self.key, x, dz, dw, db, own_ws)      # inside the launch of the next slab layer (_plan_w9_pair)
+        elif own_ws is not None and held is not None and sp.w9_hold_for.get(held[0]) == self.key:
+            # this layer's few, long workgroups in front, the waiting layer's behind them in the same grid; the reductions join the pending
+            # list in backward order, each with the flush test it would have had behind a launch of its own
+            sp.w9_held = None
+            mine, theirs = ops.conv3x3_wgrad_pair_deferred((x, dz, dw, db, own_ws), held[1:])
+            e.w9_append(sp, theirs, held[5])
+            e.w9_append(sp, mine, own_ws)
+        elif own_ws is not None:    # slab kernel now, the reduction with the other layers' at the end of the pass
+            e._release_w9(sp)
             job, nblk = ops.conv3x3_wgrad_deferred(x, dz, dw, db, own_ws)
             if job is not None:
-                sp.w9_pending.append((job, nblk))
-                sp.w9_pending_bytes += own_ws.numel()
-                if e.w9_flush_bytes and sp.w9_pending_bytes >= e.w9_flush_bytes:
-                    e._flush_w9(sp)         # (knob OCR_W9_FLUSH_MB: reduce while the slabs are still in the Infinity Cache)
+                e.w9_append(sp, (job, nblk), own_ws)
         else:
             ops.conv3x3_wgrad(x, dz, dw, dbias=db, workspace=sp.buf.get('wgrad_ws'))   # bias gradient rides on the same pass
         if p.key in sp.unpool_pools:            # through the pool in front, by the codes of ITS producer (alloc)

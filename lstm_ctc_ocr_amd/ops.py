@@ -351,6 +351,32 @@ def conv3x3_wgrad_deferred(x, dy, dw, dbias, workspace):
     return (bytes(job), nblk.value) if deferred.value else (None, 0)
 
 
+def conv3x3_wgrad_pair_supported(shape_first, shape_second):
+    """May the slab kernels of two layers, shapes (Nb, W, H, Cin, Cout), run as ONE launch with the first layer's workgroups in front
+    (host-only query, no GPU needed)?  The library's whole pairing policy: both take a slab kernel, a paired instance exists, and the first
+    layer's grid fills at most half the CUs."""
+    a, b = (ctypes.c_int * 5)(*[int(v) for v in shape_first]), (ctypes.c_int * 5)(*[int(v) for v in shape_second])
+    rc = nat.lib().ocr_conv3x3_wgrad_pair_supported(a, b)
+    if rc < 0:
+        raise nat.NativeError("ocr_conv3x3_wgrad_pair_supported failed: status %d (%s)" % (-rc, nat.status_string(-rc)))
+    return bool(rc)
+
+
+def conv3x3_wgrad_pair_deferred(first, second):
+    """conv3x3_wgrad_deferred of two layers in ONE launch; `first` / `second` = (x, dy, dw, dbias, workspace) of a pair that
+    conv3x3_wgrad_pair_supported accepts.  Returns ((job, nblocks), (job, nblocks)): what the two single launches would have returned —
+    same split counts, same slabs."""
+    args, outs = [], []
+    for x, dy, dw, dbias, workspace in (first, second):
+        Nb, W, H, Cin = x.shape
+        shape = (ctypes.c_int * 5)(Nb, W, H, Cin, dy.shape[-1])
+        args += [ptr(_dev(x)), ptr(dy), ptr(dw), ptr(dbias), shape, ptr(workspace), workspace.numel()]
+        outs.append(((ctypes.c_ubyte * 64)(), ctypes.c_int(0)))
+    call("ocr_conv3x3_wgrad_pair_defer_bf16", *args, ctypes.cast(outs[0][0], ctypes.c_void_p), ctypes.cast(outs[1][0], ctypes.c_void_p),
+         ctypes.byref(outs[0][1]), ctypes.byref(outs[1][1]), _st())
+    return tuple((bytes(job), nblk.value) for job, nblk in outs)
+
+
 def wgrad9_reduce_jobs(table, njobs, total_blocks):
     call("ocr_wgrad9_reduce_jobs", ptr(_dev(table)), njobs, total_blocks, _st())
 
