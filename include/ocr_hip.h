@@ -62,6 +62,20 @@ int ocr_ctc_loss_long(const float* activations, float* gradients /* f32 [T][N][C
                       const int* flat_labels, const int* label_lengths, const int* input_lengths,
                       int alphabet_size, int minibatch, int max_time, int max_label_len, int blank_label,
                       float* costs, void* workspace, size_t workspace_bytes, void* stream);
+/* wide alphabets, 1 <= alphabet_size <= 16384 and 1 <= max_label_len <= 255: the shapes beyond the LDS class accumulators of the two forms
+ * above.  Two launches on `stream`: one workgroup per logit row (softmax * scale into the gradients, log-probabilities of the label's slots
+ * into `workspace`), then one workgroup per sample (alpha / beta, costs, and the at most 2L+1 gradient elements per frame that are not plain
+ * softmax).  Parameters, outputs and semantics as ocr_ctc_loss_long; `workspace` is always needed (ocr_ctc_wide_workspace_size bytes:
+ * three [T][64 * slots-per-lane] float tables per sample).  ocr_ctc_wide_supported is arithmetic only and works without a GPU.
+ * OCR_STATUS_INVALID, with nothing launched, for a NULL operand (the two gradients excepted), a blank outside [0, alphabet_size), a shape
+ * ocr_ctc_wide_supported refuses, or a workspace that is short. */
+int ocr_ctc_wide_supported(int alphabet_size, int max_time, int max_label_len);
+int ocr_ctc_wide_workspace_size(int alphabet_size, int max_label_len, int max_time, int minibatch, size_t* bytes);
+int ocr_ctc_loss_wide(const float* activations, float* gradients /* f32 [T][N][C] or NULL */,
+                      void* grad_ntc_bf16 /* [N][T][C] or NULL */, float scale,
+                      const int* flat_labels, const int* label_lengths, const int* input_lengths,
+                      int alphabet_size, int minibatch, int max_time, int max_label_len, int blank_label,
+                      float* costs, void* workspace, size_t workspace_bytes, void* stream);
 /* best-path decode (argmax, collapse repeats, drop blank): the greedy counterpart of
  * tf.nn.ctc_beam_search_decoder + sparse_tensor_to_dense(default 0) at network.py:656-657 / test.py:30-31.
  * decoded: int32 [minibatch, max_time] padded with pad_value; decoded_lengths: int32 [minibatch]. */

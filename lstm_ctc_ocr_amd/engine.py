@@ -133,10 +133,13 @@ class ShapePlan(object):
             self.buf['wgrad_ws'] = torch.empty(need, dtype=torch.uint8, device=dev)
         self.T, _, self.C = self.oshape[eng.ops[-1].key]
         self.costs = torch.zeros(N, dtype=F32, device=dev)
-        self.ctc_grad = torch.empty((self.T, N, self.C), dtype=F32, device=dev)
+        path = eng.ctc_path_of(self.C, self.T)
+        self.ctc_grad = torch.empty((self.T, N, self.C) if path != 'wide' else (0,), dtype=F32, device=dev)    # (the wide form has no f32 hand-off)
         ws_bytes = ops.ctc_workspace_bytes(eng.max_label_len, self.T, N) if eng.max_label_len <= 127 else 1      # (the general kernel stops at 127)
-        if eng.ctc_path_of(self.C, self.T) == 'long':
+        if path == 'long':
             ws_bytes = max(ws_bytes, ops.ctc_long_workspace_bytes(self.C, eng.max_label_len, self.T, N))
+        elif path == 'wide':
+            ws_bytes = ops.ctc_wide_workspace_bytes(self.C, eng.max_label_len, self.T, N)
         self.ctc_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         self.decoded = torch.zeros((N, self.T), dtype=I32, device=dev)
         self.decoded_len = torch.zeros(N, dtype=I32, device=dev)
@@ -147,7 +150,7 @@ class Engine(object):
     """Owns parameters, optimiser state and per-shape plans for one Network on one GPU."""
 
     def __init__(self, net, device='cuda:0', seed=None, max_label_len=31, use_graphs=True, group=None,
-                 persistent_lstm=True, fuse_conv1_pool=True, ctc_long=True):
+                 persistent_lstm=True, fuse_conv1_pool=True, ctc_long=True, ctc_wide=True):
         from .config import cfg
         if max_label_len > self.CTC_MAX_LABEL_LEN:
             raise ValueError('max_label_len = %d: the CTC loss covers labels of at most %d characters' % (max_label_len, self.CTC_MAX_LABEL_LEN))
@@ -160,6 +163,7 @@ class Engine(object):
         self.num_features = cfg.NUM_FEATURES
         self.max_label_len = max_label_len
         self.ctc_long = ctc_long          # False: the one-launch long-label kernel is never chosen (A/B switch)
+        self.ctc_wide = ctc_wide          # False: the two-launch wide-alphabet form is never chosen (A/B switch)
         self.use_graphs = use_graphs
         self.persistent_lstm = persistent_lstm
         self.fuse_conv1_pool = fuse_conv1_pool
@@ -537,6 +541,9 @@ class Engine(object):
         elif path == 'long':
             ops.ctc_loss_long(logits, sp.labels, sp.labels_len, sp.seq_len, self.max_label_len, blank=0, want_grad=False,
                               grad_ntc_bf16=self.ops[-1].dy(sp), scale=scale, workspace=sp.ctc_ws, costs=sp.costs)
+        elif path == 'wide':
+            ops.ctc_loss_wide(logits, sp.labels, sp.labels_len, sp.seq_len, self.max_label_len, blank=0, want_grad=False,
+                              grad_ntc_bf16=self.ops[-1].dy(sp), scale=scale, workspace=sp.ctc_ws, costs=sp.costs)
         else:
             ops.ctc_loss(logits, sp.labels, sp.labels_len, sp.seq_len, self.max_label_len, blank=0, want_grad=True,
                          workspace=sp.ctc_ws, costs=sp.costs, grads=sp.ctc_grad)
@@ -553,11 +560,15 @@ class Engine(object):
 
     def ctc_path_of(self, C, T):
         """Which CTC form a plan with T frames of C classes takes: 'fast' (ctc_fast_kernel's training form, S <= 64 with its tables in
-        LDS), 'long' (ctc_long_kernel, one launch, labels up to 255) or 'general' (scan + one-wave kernel + transpose)."""
+        LDS), 'long' (ctc_long_kernel, one launch, labels up to 255), 'wide' (rows kernel + samples kernel, up to 16384 classes: only the
+        shapes neither of those two kernels covers) or 'general' (scan + one-wave kernel + transpose)."""
         if ops.ctc_train_supported(C, T, self.max_label_len):
             return 'fast'
-        if self.ctc_long and ops.ctc_long_supported(C, T, self.max_label_len):
+        long_covers = ops.ctc_long_supported(C, T, self.max_label_len)
+        if self.ctc_long and long_covers:
             return 'long'
+        if self.ctc_wide and not long_covers and ops.ctc_wide_supported(C, T, self.max_label_len):
+            return 'wide'
         return 'general'
 
     def ctc_path(self, N, W):

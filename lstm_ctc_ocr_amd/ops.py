@@ -91,6 +91,34 @@ def ctc_loss_long(acts, labels, label_lengths, input_lengths, max_label_len, bla
     return costs, (grads if want_grad else None)
 
 
+def ctc_wide_supported(C, T, max_label_len):
+    """C <= 16384 classes, labels of up to 255 characters (host arithmetic only)."""
+    return bool(nat.lib().ocr_ctc_wide_supported(C, T, max_label_len))
+
+
+def ctc_wide_workspace_bytes(C, max_label_len, max_time, minibatch):
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_wide_workspace_size", C, max_label_len, max_time, minibatch, ctypes.byref(sz))
+    return sz.value
+
+
+def ctc_loss_wide(acts, labels, label_lengths, input_lengths, max_label_len, blank=0, want_grad=True, grad_ntc_bf16=None, scale=1.0,
+                  workspace=None, costs=None, grads=None):
+    """Wide alphabets (up to 16384 classes) in two launches, one workgroup per logit row and one per sample: costs, the f32 [T, N, C]
+    gradient (want_grad) and / or scale * gradient as bf16 [N, T, C] (grad_ntc_bf16).  -> (costs, f32 gradient or None)."""
+    T, N, C = acts.shape
+    _dev(acts)
+    if workspace is None:
+        workspace = torch.empty(ctc_wide_workspace_bytes(C, max_label_len, T, N), dtype=torch.uint8, device=acts.device)
+    if costs is None:
+        costs = torch.empty(N, dtype=F32, device=acts.device)
+    if want_grad and grads is None:
+        grads = torch.empty_like(acts)
+    call("ocr_ctc_loss_wide", ptr(acts), ptr(grads) if want_grad else None, ptr(grad_ntc_bf16), float(scale), ptr(labels),
+         ptr(label_lengths), ptr(input_lengths), C, N, T, max_label_len, blank, ptr(costs), ptr(workspace), workspace.numel(), _st())
+    return costs, (grads if want_grad else None)
+
+
 def ctc_greedy_decode(acts, input_lengths, blank=0, pad_value=0):
     T, N, C = acts.shape
     out = torch.empty((N, T), dtype=torch.int32, device=acts.device)
