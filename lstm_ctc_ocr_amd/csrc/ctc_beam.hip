@@ -12,6 +12,15 @@
 // compaction into the next beam -> trie bookkeeping (node pool in a caller-owned workspace).  This path runs at
 // validation / test time only; it is latency-, not throughput-critical.
 //
+// Node identity is per PREFIX, for the whole decode: a beam entry finds its parent's slot through nslot[npar[node]], and that is the
+// only thing that tells step (b) which entry feeds it and step (c) which children need no candidate.  A prefix P can drop out of the
+// beam while its extension Q = P + c stays, and come back frames later as a child of its own parent (flat logits do this all the time,
+// peaky ones hardly ever).  If P then got a fresh node, Q would still hang off the old one: it would never receive P's mass again and
+// (P, c) would be scored as a new candidate - a second copy of Q with part of the mass - where TF keeps a child in its parent's
+// `children` map for good and restarts the same object from zero.  So step (f) looks every admitted child (parent node, label) up among
+// the existing nodes (one pass over the pool per frame) and puts it back on its node with (p_blank, p_label) = (0, candidate score); only
+// a prefix never seen before takes a new node.  The pool bound T*K + 2 holds all the more.
+//
 // Two kernels share that body.  The TABLE kernel (WIDE = false) scores every (beam entry, class) pair and answers "is child (b, c)
 // already in the beam" from a 16-bit [K][C] table: about 6*K*C bytes of LDS, which at K = 100 ends at 259 classes.  The WIDE kernel
 // (WIDE = true) has no K*C term.  Per frame it first selects S, the M = min(K + 1, C - 1) non-blank classes with the largest lp (ties
@@ -253,18 +262,46 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         __syncthreads();
         // leaves' new (p_blank, p_label) live in registers of thread s; publish them through the dead half of the beam arrays
         if (tid < nb) { pb2[tid] = my_npb; pnb2[tid] = my_npnb; }     // temporarily indexed by OLD slot
+        float r_pb = NEGINF, r_pnb = NEGINF, r_tot = NEGINF; int r_node = -1, r_last = -1, r_src = -1;
+        if (tid < nnew) { r_src = sel_src[tid]; r_tot = cand[r_src]; }
+        __syncthreads();
+        // One node per prefix: a child that enters the beam may be a prefix that was in it before (see the header).  Its node is found by
+        // one pass over the pool: node `id` is such a child iff its parent sits in the (old) beam at slot b and candidate (b, nlab[id])
+        // was selected.  cand and sel_src are dead by now: cand becomes the map candidate -> new slot, sel_src the node each new slot reuses.
+        int* cslot = (int*)cand;
+        for (int i = nb + tid; i < ncand; i += 256) cslot[i] = -1;
+        __syncthreads();
+        if (tid < nnew) { sel_src[tid] = -1; if (r_src >= nb) cslot[r_src] = tid; }
+        __syncthreads();
+        const int nalloc = s_misc[1];
+        for (int id = 1 + tid; id < nalloc; id += 256) {
+            const int b = nslot[npar[id]];                  // still the old generation's slots
+            if (b < 0) continue;
+            int j = nlab[id];
+            if constexpr (WIDE) {
+                const int c = j;
+                int l = 0, r = M;                            // first j with S[j] >= c
+                while (l < r) { const int mid = (l + r) >> 1; if (sel_cls[mid] < c) l = mid + 1; else r = mid; }
+                j = (l < M && sel_cls[l] == c) ? l : -1;
+            }
+            if (j < 0) continue;
+            const int s = cslot[nb + b * M + j];
+            if (s >= 0) sel_src[s] = id;
+        }
+        __syncthreads();
         if (tid < nb) nslot[node[tid]] = -1;                           // everything is out of the beam until re-registered
         __syncthreads();
-        float r_pb = NEGINF, r_pnb = NEGINF, r_tot = NEGINF; int r_node = -1, r_last = -1;
         if (tid < nnew) {
-            const int i = sel_src[tid];
-            r_tot = cand[i];
+            const int i = r_src;
             if (i < nb) {                                   // surviving leaf
                 r_node = node[i]; r_last = last[i]; r_pb = pb2[i]; r_pnb = pnb2[i];
-            } else {                                        // new child of leaf b with label c
+            } else {                                        // child of leaf b with label c: back on its old node, or new
                 const int b = (i - nb) / M, c = WIDE ? sel_cls[(i - nb) - b * M] : (i - nb) - b * M;
-                const int id = atomicAdd(&s_misc[1], 1);
-                npar[id] = node[b]; nlab[id] = (short)c;
+                int id = sel_src[tid];
+                if (id < 0) {
+                    id = atomicAdd(&s_misc[1], 1);
+                    npar[id] = node[b]; nlab[id] = (short)c;
+                }
                 r_node = id; r_last = c; r_pb = NEGINF; r_pnb = r_tot;
             }
         }
