@@ -76,6 +76,28 @@ int ocr_ctc_loss_wide(const float* activations, float* gradients /* f32 [T][N][C
                       const int* flat_labels, const int* label_lengths, const int* input_lengths,
                       int alphabet_size, int minibatch, int max_time, int max_label_len, int blank_label,
                       float* costs, void* workspace, size_t workspace_bytes, void* stream);
+/* lexicon scoring: costs[n][k] = -log p(candidate k | logits of sample n) for num_candidates strings against ONE set of logits (no copy per
+ * candidate), 1 <= alphabet_size <= 16384, max_time >= 1, 0 <= max_label_len <= 255, 1 <= num_candidates <= 65536 (ocr_ctc_score_supported:
+ * arithmetic only, works without a GPU).  Three launches on `stream`: the log-sum-exp of every logit row a sample owns into `workspace`
+ * (ocr_ctc_score_workspace_size bytes: a float per row), one wave per (sample, candidate) running the alpha recursion in registers, one
+ * workgroup per sample for the arg-min and the normaliser.
+ *   cand_labels  : int32 [num_candidates][max_label_len], dense; cand_lengths: int32 [num_candidates].  sample_stride = 0: one lexicon shared
+ *                  by every sample.  sample_stride = num_candidates: a lexicon per sample, labels [minibatch][num_candidates][max_label_len],
+ *                  lengths [minibatch][num_candidates].  Words beyond a candidate's length are never read.
+ *   costs        : f32 [minibatch][num_candidates].  +inf, never 0, for a candidate that cannot be emitted: input length <= 0, length + repeats
+ *                  above the input length, a length outside [0, max_label_len], or a label inside the length that is outside
+ *                  [0, alphabet_size) or equals blank_label (such a label is never used as an index).  Length 0 is the all-blank path.
+ *   best         : int32 [minibatch] arg-min of the costs (lowest index on ties; -1 when every cost is +inf); best_cost: f32 [minibatch], that
+ *                  cost; log_norm: f32 [minibatch] = log sum_k exp(-costs[n][k]) (-inf when none is finite), so candidate k's posterior within
+ *                  the lexicon is exp(-costs[n][k] - log_norm[n]).  The three may be NULL together: the third launch is skipped.
+ * OCR_STATUS_INVALID, with nothing launched, for a NULL required operand, best / best_cost / log_norm partly NULL, a blank outside
+ * [0, alphabet_size), a sample_stride other than 0 or num_candidates, a short workspace, minibatch > 65535, or a shape
+ * ocr_ctc_score_supported refuses. */
+int ocr_ctc_score_supported(int alphabet_size, int max_time, int max_label_len, int num_candidates);
+int ocr_ctc_score_workspace_size(int alphabet_size, int max_time, int minibatch, size_t* bytes);
+int ocr_ctc_score(const float* activations, const int* input_lengths, const int* cand_labels, const int* cand_lengths, int sample_stride,
+                  int alphabet_size, int minibatch, int max_time, int num_candidates, int max_label_len, int blank_label,
+                  float* costs, int* best, float* best_cost, float* log_norm, void* workspace, size_t workspace_bytes, void* stream);
 /* best-path decode (argmax, collapse repeats, drop blank): the greedy counterpart of
  * tf.nn.ctc_beam_search_decoder + sparse_tensor_to_dense(default 0) at network.py:656-657 / test.py:30-31.
  * decoded: int32 [minibatch, max_time] padded with pad_value; decoded_lengths: int32 [minibatch]. */

@@ -34,6 +34,9 @@ _SIGS = {
     "ocr_ctc_wide_supported": ([_I, _I, _I], _I),
     "ocr_ctc_wide_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_loss_wide": ([_P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, ctypes.c_size_t, _P], _I),
+    "ocr_ctc_score_supported": ([_I, _I, _I, _I], _I),
+    "ocr_ctc_score_workspace_size": ([_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
+    "ocr_ctc_score": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "ocr_ctc_greedy_decode": ([_P, _P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "ocr_ctc_beam_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_beam_decode": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),

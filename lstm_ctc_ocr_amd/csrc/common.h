@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <math.h>
 #include <atomic>
 
 #define OCR_WAVE 64
@@ -143,6 +144,15 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+#define NEG_INF (-INFINITY)
+// whole-wave shifts by one lane as DPP moves (wave_shr:1 / wave_shl:1, one VALU instruction; the lane shifted in takes `fill`)
+// instead of ds_bpermute round trips through the LDS crossbar: they sit on the T-sequential critical path of the recursions
+__device__ __forceinline__ float wave_shr1(float v, float fill) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float wave_shl1(float v, float fill) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
 }
 // Block-level reduction over the row lanes of a (row lane) x (channel group) thread layout, followed by one
 // atomic (STORE = false) or one plain store (STORE = true: dst is this block's private partial row) per channel.

@@ -17,8 +17,7 @@
 #include "common.h"
 #include <math.h>
 
-#define NEG_INF (-INFINITY)
-
+// (NEG_INF and the DPP wave shifts wave_shr1 / wave_shl1 are in common.h, shared with ctc_score.hip)
 __device__ __forceinline__ float lse2(float a, float b) {
     float m = fmaxf(a, b);
     if (m == NEG_INF) return NEG_INF;
@@ -41,15 +40,6 @@ __device__ __forceinline__ float lse3_fast(float a, float b, float c) {
     float m = fmaxf(fmaxf(a, b), c);
     if (m == NEG_INF) return NEG_INF;
     return m + __logf(__expf(a - m) + __expf(b - m) + __expf(c - m));
-}
-
-// whole-wave shifts by one lane as DPP moves (wave_shr:1 / wave_shl:1, one VALU instruction; the lane shifted in takes `fill`)
-// instead of ds_bpermute round trips through the LDS crossbar: they sit on the T-sequential critical path of the recursions
-__device__ __forceinline__ float wave_shr1(float v, float fill) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_shl1(float v, float fill) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
 }
 
 // VT = extended-label slots per lane (S <= 64*VT).

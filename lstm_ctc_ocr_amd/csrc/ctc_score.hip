@@ -1,0 +1,295 @@
+// Lexicon scoring under CTC for gfx950: costs[n][k] = -log p(candidate k | logits of sample n) for K candidate strings against ONE set of
+// logits [T, N, C], the arg-min per sample and the lexicon's log-normaliser.  The forward half of CTC with the logits shared: the loss kernels
+// of ctc.hip take one label per sample (K candidates would mean K copies of the logits) and report an infeasible label as cost 0, which would
+// win every arg-min; here an impossible candidate costs +inf.
+//
+// Three launches, ordered by the stream (no workgroup waits on another):
+//   ctc_score_rows_kernel    lse[t][n] = log sum_c exp(act[t][n][c]) for the rows a sample owns (t < Tn), the row held in registers (16 elements a
+//                            thread, as ctc_wide_rows_kernel): one workgroup of 256 / 512 / 1024 threads per row, or, for C <= 1024, one WAVE per
+//                            row and four rows per workgroup (no LDS, no barrier).  Rows with t >= Tn are neither read nor written.
+//   ctc_score_cands_kernel   one wave per (sample, candidate), four per workgroup.  alpha of the S = 2L+1 slots lives in registers, lane-contiguous
+//                            (slot s in lane s / VT, register s % VT); the s-1 / s-2 neighbours are the lane's own registers or come from the lane
+//                            below through the DPP wave shift.  No LDS and no barrier.  Per frame a lane gathers act[t][n][label] for its odd slots
+//                            and every lane reads the blank's logit and lse[t][n] (one address each); the loads of frame t+1 are issued before the
+//                            log-add-exp of frame t.
+//   ctc_score_best_kernel    one workgroup per sample: arg-min (lowest index on ties, -1 when no candidate is feasible), its cost, and
+//                            log sum_k exp(-cost) (-inf when none is finite).
+// Infeasible means +inf, never 0: Tn <= 0, L + repeats > Tn, L outside [0, max_label_len], or a label inside the candidate's length that is
+// outside [0, C) or equals the blank.  Such a label is never used as an index, and words beyond a candidate's length are never read.
+#include "common.h"
+#include <math.h>
+
+constexpr int SCORE_MAX_C = 16384;
+constexpr int SCORE_MAX_LABEL = 255;
+constexpr int SCORE_MAX_K = 65536;
+constexpr int SCORE_PER = 16;            // row elements a thread of the rows kernel keeps
+constexpr int SCORE_WAVE_ROW_C = 64 * SCORE_PER;      // up to here a row fits one wave
+constexpr int SCORE_CW = 4;              // candidates (waves) per workgroup of the candidates kernel
+
+// log(e^a + e^b + e^c) as straight-line code on v_exp_f32 / v_log_f32 (ctc.hip's lse3_flat): with every input -inf the maximum is replaced by 0,
+// the sum is 0 and the logarithm -inf, so no branch sits on the chain
+__device__ __forceinline__ float score_lse3(float a, float b, float c) {
+    const float m = fmaxf(fmaxf(a, b), c);
+    const float m0 = (m == NEG_INF) ? 0.f : m;
+    constexpr float LOG2E = 1.44269504088896341f, LN2 = 0.693147180559945309f;
+    const float sum = __builtin_amdgcn_exp2f((a - m0) * LOG2E) + __builtin_amdgcn_exp2f((b - m0) * LOG2E) + __builtin_amdgcn_exp2f((c - m0) * LOG2E);
+    return m0 + __builtin_amdgcn_logf(sum) * LN2;
+}
+
+// TPR threads hold one row: TPR == NT (one row per workgroup, two barriers) or TPR == 64 (one row per wave, NT / 64 rows per workgroup).
+// VEC consecutive elements per load: 8 / 4 need C % VEC == 0 and a 16-byte aligned tensor.
+template <int NT, int TPR, int VEC>
+__global__ __launch_bounds__(NT) void ctc_score_rows_kernel(const float* __restrict__ act, const int* __restrict__ input_len, int T, int N, int C,
+                                                            float* __restrict__ lse_out) {
+    constexpr int RPB = NT / TPR, NCH = SCORE_PER / VEC, NW = TPR / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long r = (long)blockIdx.x * RPB + (RPB > 1 ? wave : 0);
+    const int rt = RPB > 1 ? lane : tid;                  // thread within the row
+    if (r >= (long)T * N) return;                         // (per wave when RPB > 1, per workgroup otherwise: no barrier is skipped by a part)
+    const int t = (int)(r / N), n = (int)(r - (long)t * N);
+    if (t >= min(input_len[n], T)) return;                // not a frame of this sample: neither read nor written
+    const float* row = act + (size_t)r * C;
+
+    float v[SCORE_PER];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+        const int k = (i * TPR + rt) * VEC;
+        const bool in = k < C;                            // (covers k + VEC <= C: C is a multiple of VEC)
+        if constexpr (VEC == 1) v[i] = in ? row[k] : NEG_INF;
+        else {
+#pragma unroll
+            for (int q = 0; q < VEC / 4; ++q) {
+                const f32x4 x = in ? *(const f32x4*)(row + k + 4 * q) : (f32x4){NEG_INF, NEG_INF, NEG_INF, NEG_INF};
+                v[i * VEC + 4 * q] = x.x; v[i * VEC + 4 * q + 1] = x.y; v[i * VEC + 4 * q + 2] = x.z; v[i * VEC + 4 * q + 3] = x.w;
+            }
+        }
+    }
+    float m = v[0];
+#pragma unroll
+    for (int j = 1; j < SCORE_PER; ++j) m = fmaxf(m, v[j]);
+    m = wave_max(m);
+    __shared__ float s_max[NW > 1 ? NW : 1], s_sum[NW > 1 ? NW : 1];
+    if constexpr (NW > 1) {
+        if (lane == 0) s_max[wave] = m;
+        __syncthreads();
+        m = s_max[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) m = fmaxf(m, s_max[w]);
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < SCORE_PER; ++j) sum += __expf(v[j] - m);          // (elements past C: exp(-inf) = 0)
+    sum = wave_sum(sum);
+    if constexpr (NW > 1) {
+        if (lane == 0) s_sum[wave] = sum;
+        __syncthreads();
+        sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum += s_sum[w];
+    }
+    if (rt == 0) lse_out[r] = m + logf(sum);
+}
+
+// VT = extended-label slots per lane (S = 2L+1 <= 64 * VT for every L <= max_label_len: chosen on the host)
+template <int VT>
+__global__ __launch_bounds__(64 * SCORE_CW) void ctc_score_cands_kernel(
+    const float* __restrict__ act, const float* __restrict__ lse, const int* __restrict__ input_len, const int* __restrict__ cand_labels,
+    const int* __restrict__ cand_len, int sample_stride, int T, int N, int C, int K, int Lmax, int blank, float* __restrict__ costs) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = blockIdx.y, k = blockIdx.x * SCORE_CW + wave;
+    if (k >= K) return;                                   // (whole waves; the kernel has no barrier)
+    const size_t cand = (size_t)n * sample_stride + k;
+    const int L = cand_len[cand];
+    const int Tn = min(input_len[n], T);
+    float* out = costs + (size_t)n * K + k;
+    if (L < 0 || L > Lmax || Tn <= 0) { if (lane == 0) *out = INFINITY; return; }
+    const int* labels = cand_labels + cand * Lmax;
+    const int S = 2 * L + 1;
+
+    // this lane's slots: the label of an odd slot inside the candidate (words at or beyond L are not read), whether it may take the s-2 step
+    int lab[VT];
+    bool skip[VT], in[VT];
+    int bad = 0, rep = 0;
+#pragma unroll
+    for (int v = 0; v < VT; ++v) {
+        const int s = lane * VT + v, j = s >> 1;
+        const bool odd = VT > 1 ? (v & 1) : (lane & 1);
+        const bool has = odd && j < L;
+        const int c = has ? labels[j] : blank;
+        const int before = (has && j >= 1) ? labels[j - 1] : -1;
+        if (has && ((unsigned)c >= (unsigned)C || c == blank)) bad = 1;
+        if (has && j >= 1 && c == before) rep++;
+        in[v] = s < S;
+        skip[v] = has && j >= 1 && c != before;
+        lab[v] = (has && (unsigned)c < (unsigned)C) ? c : blank;          // an out-of-range label is never an index
+    }
+    bad = __any(bad);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rep += __shfl_xor(rep, o, 64);
+    if (bad || L + rep > Tn) { if (lane == 0) *out = INFINITY; return; }
+
+    const size_t tstride = (size_t)N * C;
+    const float* a_n = act + (size_t)n * C;
+    const float* lse_n = lse + n;
+    // logy of this lane's slots at frame t: gathered logit (odd slots) or the blank's (one address for the wave) minus the row's log-sum-exp
+    float g[VT], gb, gl;
+#define SCORE_LOAD(t_)                                                                                         \
+    do {                                                                                                       \
+        const float* row_ = a_n + (size_t)(t_) * tstride;                                                      \
+        gb = row_[blank]; gl = lse_n[(size_t)(t_) * N];                                                        \
+        _Pragma("unroll") for (int v = 0; v < VT; ++v) {                                                       \
+            const bool odd_ = VT > 1 ? (v & 1) : (lane & 1);                                                   \
+            g[v] = odd_ ? row_[lab[v]] : 0.f;                                                                  \
+        }                                                                                                      \
+    } while (0)
+#define SCORE_LOGY(dst)                                                                                        \
+    _Pragma("unroll") for (int v = 0; v < VT; ++v) {                                                           \
+        const bool odd_ = VT > 1 ? (v & 1) : (lane & 1);                                                       \
+        dst[v] = in[v] ? (odd_ ? g[v] : gb) - gl : NEG_INF;                                                    \
+    }
+    float a[VT], ly[VT];
+    SCORE_LOAD(0);
+    SCORE_LOGY(ly);
+#pragma unroll
+    for (int v = 0; v < VT; ++v) a[v] = (lane * VT + v < 2) ? ly[v] : NEG_INF;          // (slot 1 of an empty candidate: in[] is false, -inf)
+    if (Tn > 1) { SCORE_LOAD(1); SCORE_LOGY(ly); }
+    for (int t = 1; t < Tn; ++t) {
+        SCORE_LOAD(min(t + 1, Tn - 1));                   // frame t + 1, in flight during the step below
+        float p1, p2;
+        if constexpr (VT == 1) { p1 = wave_shr1(a[0], NEG_INF); p2 = wave_shr1(p1, NEG_INF); }
+        else { p1 = wave_shr1(a[VT - 1], NEG_INF); p2 = wave_shr1(a[VT > 1 ? VT - 2 : 0], NEG_INF); }
+        float na[VT];
+#pragma unroll
+        for (int v = 0; v < VT; ++v) {
+            const float x1 = v >= 1 ? a[v >= 1 ? v - 1 : 0] : p1;
+            const float x2 = v >= 2 ? a[v >= 2 ? v - 2 : 0] : (v == 1 ? p1 : p2);
+            na[v] = score_lse3(a[v], x1, skip[v] ? x2 : NEG_INF) + ly[v];
+        }
+#pragma unroll
+        for (int v = 0; v < VT; ++v) a[v] = na[v];
+        SCORE_LOGY(ly);
+    }
+#undef SCORE_LOAD
+#undef SCORE_LOGY
+    float x1 = NEG_INF, x2 = NEG_INF;
+#pragma unroll
+    for (int v = 0; v < VT; ++v) {
+        if (v == ((S - 1) & (VT - 1))) x1 = a[v];
+        if (S >= 2 && v == ((S - 2) & (VT - 1))) x2 = a[v];
+    }
+    const float e1 = __shfl(x1, (S - 1) / VT, 64);
+    const float e2 = (S >= 2) ? __shfl(x2, (S - 2) / VT, 64) : NEG_INF;
+    if (lane == 0) {
+        const float m = fmaxf(e1, e2);
+        *out = (m == NEG_INF) ? INFINITY : -(m + logf(expf(e1 - m) + expf(e2 - m)));
+    }
+}
+
+constexpr int SCORE_BEST_NT = 256;
+__global__ __launch_bounds__(SCORE_BEST_NT) void ctc_score_best_kernel(const float* __restrict__ costs, int K, int* __restrict__ best,
+                                                                       float* __restrict__ best_cost, float* __restrict__ log_norm) {
+    constexpr int NW = SCORE_BEST_NT / 64;
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* c_n = costs + (size_t)n * K;
+    __shared__ float s_c[NW], s_sum[NW];
+    __shared__ int s_i[NW];
+    float bc = INFINITY;
+    int bi = 0x7fffffff;
+    for (int k = tid; k < K; k += SCORE_BEST_NT) {
+        const float c = c_n[k];
+        if (c < bc) { bc = c; bi = k; }                   // (ascending k per thread: strict < keeps the lowest index)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float oc = __shfl_xor(bc, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (oc < bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
+    }
+    if (lane == 0) { s_c[wave] = bc; s_i[wave] = bi; }
+    __syncthreads();
+    bc = s_c[0]; bi = s_i[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w)
+        if (s_c[w] < bc || (s_c[w] == bc && s_i[w] < bi)) { bc = s_c[w]; bi = s_i[w]; }
+    const bool any = bc < INFINITY;
+    float sum = 0.f;
+    if (any)
+        for (int k = tid; k < K; k += SCORE_BEST_NT) sum += expf(bc - c_n[k]);          // (+inf cost: exp(-inf) = 0)
+    sum = wave_sum(sum);
+    if (lane == 0) s_sum[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum += s_sum[w];
+        best[n] = any ? bi : -1;
+        best_cost[n] = bc;
+        log_norm[n] = any ? logf(sum) - bc : NEG_INF;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// C ABI (declared in include/ocr_hip.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ocr_ctc_score_supported(int alphabet_size, int max_time, int max_label_len, int num_candidates) {
+    return alphabet_size >= 1 && alphabet_size <= SCORE_MAX_C && max_time >= 1 && max_label_len >= 0 && max_label_len <= SCORE_MAX_LABEL &&
+           num_candidates >= 1 && num_candidates <= SCORE_MAX_K;
+}
+// the lse[T][N] table
+extern "C" int ocr_ctc_score_workspace_size(int alphabet_size, int max_time, int minibatch, size_t* bytes) {
+    if (!bytes || minibatch <= 0 || !ocr_ctc_score_supported(alphabet_size, max_time, 0, 1) || (long)minibatch * max_time > 0x7fffffffL)
+        return OCR_ERR_INVALID;
+    *bytes = ((size_t)minibatch * max_time * sizeof(float) + 255) & ~(size_t)255;
+    return OCR_OK;
+}
+template <int NT, int TPR, int VEC>
+static void ctc_score_rows_launch(const float* act, const int* il, int T, int N, int C, float* lse, hipStream_t stream) {
+    const long rows = (long)T * N;
+    ctc_score_rows_kernel<NT, TPR, VEC><<<ceil_div(rows, NT / TPR), NT, 0, stream>>>(act, il, T, N, C, lse);
+}
+extern "C" int ocr_ctc_score(const float* activations, const int* input_lengths, const int* cand_labels, const int* cand_lengths, int sample_stride,
+                             int alphabet_size, int minibatch, int max_time, int num_candidates, int max_label_len, int blank_label, float* costs,
+                             int* best, float* best_cost, float* log_norm, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!activations || !input_lengths || !cand_labels || !cand_lengths || !costs || !workspace) return OCR_ERR_INVALID;
+    const int outs = (best != nullptr) + (best_cost != nullptr) + (log_norm != nullptr);
+    if (outs != 0 && outs != 3) return OCR_ERR_INVALID;
+    if (!ocr_ctc_score_supported(alphabet_size, max_time, max_label_len, num_candidates)) return OCR_ERR_INVALID;
+    if (blank_label < 0 || blank_label >= alphabet_size || (sample_stride != 0 && sample_stride != num_candidates)) return OCR_ERR_INVALID;
+    if (minibatch > 65535) return OCR_ERR_INVALID;        // the candidates launch has the sample in grid.y
+    size_t need = 0;
+    if (ocr_ctc_score_workspace_size(alphabet_size, max_time, minibatch, &need) != OCR_OK || workspace_bytes < need) return OCR_ERR_INVALID;
+    const int C = alphabet_size, N = minibatch, T = max_time, K = num_candidates;
+    float* lse = (float*)workspace;
+
+    const bool al16 = ((uintptr_t)activations & 15) == 0;
+    const int VEC = (al16 && C % 8 == 0) ? 8 : (al16 && C % 4 == 0) ? 4 : 1;
+#define SCORE_ROWS(NT, TPR)                                                                       \
+    do {                                                                                          \
+        if (VEC == 8) ctc_score_rows_launch<NT, TPR, 8>(activations, input_lengths, T, N, C, lse, stream);       \
+        else if (VEC == 4) ctc_score_rows_launch<NT, TPR, 4>(activations, input_lengths, T, N, C, lse, stream);  \
+        else ctc_score_rows_launch<NT, TPR, 1>(activations, input_lengths, T, N, C, lse, stream);                \
+    } while (0)
+    // a wave per row while a wave's registers hold it (no barrier, four rows per workgroup); else the smallest workgroup that holds the row
+    if (C <= SCORE_WAVE_ROW_C) SCORE_ROWS(256, 64);
+    else if (C <= 256 * SCORE_PER) SCORE_ROWS(256, 256);
+    else if (C <= 512 * SCORE_PER) SCORE_ROWS(512, 512);
+    else SCORE_ROWS(1024, 1024);
+#undef SCORE_ROWS
+    OCR_CHECK_LAUNCH();
+
+    const dim3 grid(ceil_div(K, SCORE_CW), N);
+    const int SMAX = 2 * max_label_len + 1;
+#define SCORE_CANDS(V)                                                                                                            \
+    ctc_score_cands_kernel<V><<<grid, 64 * SCORE_CW, 0, stream>>>(activations, lse, input_lengths, cand_labels, cand_lengths, sample_stride, T, N, C, K, \
+                                                                  max_label_len, blank_label, costs)
+    if (SMAX <= 64) SCORE_CANDS(1); else if (SMAX <= 128) SCORE_CANDS(2); else if (SMAX <= 256) SCORE_CANDS(4); else SCORE_CANDS(8);
+#undef SCORE_CANDS
+    OCR_CHECK_LAUNCH();
+
+    if (outs == 3) {
+        ctc_score_best_kernel<<<N, SCORE_BEST_NT, 0, stream>>>(costs, K, best, best_cost, log_norm);
+        OCR_CHECK_LAUNCH();
+    }
+    return OCR_OK;
+}

@@ -833,12 +833,18 @@ class Engine(object):
         self._run(sp, 'fwd')
         return self.ops[-1].y(sp)
 
-    def decode(self, data, seq_len, method='beam', beam_width=100):
+    def decode(self, data, seq_len, method='beam', beam_width=100, lexicon=None):
         """Decoded label lists with zeros dropped (what accuracy_calculation / decodeRes see).
-        method='beam'  : the reference's decoder — tf.nn.ctc_beam_search_decoder(beam 100, merge_repeated=True), whose
-                         blank is class C-1; class 0 is an ordinary symbol that sparse_to_dense/ignore_value=0 strip later
-                         (network.py:656-657, training.py:32).
-        method='greedy': best path with blank 0."""
+        method='beam'   : the reference's decoder — tf.nn.ctc_beam_search_decoder(beam 100, merge_repeated=True), whose
+                          blank is class C-1; class 0 is an ordinary symbol that sparse_to_dense/ignore_value=0 strip later
+                          (network.py:656-657, training.py:32).
+        method='greedy' : best path with blank 0.
+        method='lexicon': the likeliest string of `lexicon` (label lists, blank 0) under CTC; [] for a sample none of them fits."""
+        if method == 'lexicon':
+            if lexicon is None:
+                raise ValueError("decode(method='lexicon') needs a lexicon")
+            _, best, _, _ = self.score(data, seq_len, lexicon, blank=0)
+            return [[int(v) for v in lexicon[b] if v != 0] if b >= 0 else [] for b in best]
         sp = self.plan(data.shape[0], data.shape[1])
         self._bind(sp, data, seq_len)
         self._run(sp, 'fwd')
@@ -850,6 +856,37 @@ class Engine(object):
         out = out.cpu().numpy()
         lens = lens.cpu().numpy()
         return [[int(v) for v in out[i, :lens[i]] if v != 0] for i in range(out.shape[0])]
+
+    SCORE_MAX_LABEL_LEN = 255
+
+    def _pack_lexicon(self, lexicon):
+        """Device int32 [K, Lmax] labels and [K] lengths of a list of label lists; packed once per lexicon object (the last one is kept)."""
+        held = getattr(self, '_lexicon', None)
+        if held is not None and held[0] is lexicon:
+            return held[1], held[2]
+        if len(lexicon) == 0:
+            raise ValueError('empty lexicon')
+        lens = np.array([len(l) for l in lexicon], np.int32)
+        if lens.max() > self.SCORE_MAX_LABEL_LEN:
+            raise ValueError('lexicon entry of %d labels (at most %d)' % (lens.max(), self.SCORE_MAX_LABEL_LEN))
+        dense = np.zeros((len(lexicon), max(int(lens.max()), 1)), np.int32)
+        for k, l in enumerate(lexicon):
+            dense[k, :len(l)] = l
+        labels, lengths = torch.from_numpy(dense).to(self.device), torch.from_numpy(lens).to(self.device)
+        self._lexicon = (lexicon, labels, lengths)
+        return labels, lengths
+
+    def score(self, data, seq_len, lexicon, blank=0):
+        """CTC costs of every string of `lexicon` (a list of label lists in the training convention: blank 0, classes from 1) for every sample,
+        from one forward pass: -> (costs [N, K] float32, +inf for a string the sample cannot emit; best [N] int32, -1 where none can;
+        best_cost [N]; log_norm [N] = log sum_k exp(-costs)) as numpy arrays.  exp(-costs - log_norm[:, None]) is the posterior within
+        the lexicon."""
+        labels, lengths = self._pack_lexicon(lexicon)
+        sp = self.plan(data.shape[0], data.shape[1])
+        self._bind(sp, data, seq_len)
+        self._run(sp, 'fwd')
+        logits = self.ops[-1].y(sp)
+        return tuple(v.cpu().numpy() for v in ops.ctc_score(logits, sp.seq_len, labels, lengths, blank=blank))
 
     def setup_optimizer(self, solver=None, lr=None):
         c = self.cfg.TRAIN

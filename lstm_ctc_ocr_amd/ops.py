@@ -119,6 +119,46 @@ def ctc_loss_wide(acts, labels, label_lengths, input_lengths, max_label_len, bla
     return costs, (grads if want_grad else None)
 
 
+def ctc_score_supported(C, T, max_label_len, K):
+    """C <= 16384 classes, candidates of up to 255 characters, up to 65536 of them (host arithmetic only)."""
+    return bool(nat.lib().ocr_ctc_score_supported(C, T, max_label_len, K))
+
+
+def ctc_score_workspace_bytes(C, max_time, minibatch):
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_score_workspace_size", C, max_time, minibatch, ctypes.byref(sz))
+    return sz.value
+
+
+def ctc_score(acts, input_lengths, lexicon, lexicon_lengths, blank=0, per_sample=False, workspace=None, costs=None, want_best=True):
+    """CTC costs of K candidate strings against one set of logits: acts f32 [T, N, C] unnormalised; lexicon int32 [K, Lmax] with lengths [K],
+    shared by every sample, or [N, K, Lmax] with lengths [N, K] (per_sample).  -> (costs [N, K] f32, +inf for a candidate that cannot be
+    emitted; best [N] i32, -1 where no candidate can; best_cost [N] f32; log_norm [N] f32 = log sum_k exp(-costs)); the last three are None
+    when want_best is False."""
+    T, N, C = acts.shape
+    _dev(acts)
+    want = 3 if per_sample else 2
+    if lexicon.dim() != want or lexicon_lengths.dim() != want - 1 or tuple(lexicon.shape[:-1]) != tuple(lexicon_lengths.shape) or \
+            (per_sample and lexicon.shape[0] != N):
+        raise ValueError('lexicon %s / lengths %s do not fit a %s lexicon for %d samples'
+                         % (tuple(lexicon.shape), tuple(lexicon_lengths.shape), 'per-sample' if per_sample else 'shared', N))
+    K, Lmax = int(lexicon.shape[-2]), int(lexicon.shape[-1])
+    if workspace is None:
+        workspace = torch.empty(ctc_score_workspace_bytes(C, T, N), dtype=torch.uint8, device=acts.device)
+    if costs is None:
+        costs = torch.empty((N, K), dtype=F32, device=acts.device)
+    best = best_cost = log_norm = None
+    if want_best:
+        best = torch.empty(N, dtype=torch.int32, device=acts.device)
+        best_cost = torch.empty(N, dtype=F32, device=acts.device)
+        log_norm = torch.empty(N, dtype=F32, device=acts.device)
+    # (a lexicon of empty strings only has Lmax = 0 and no storage: any non-NULL address does, no word of it is read)
+    call("ocr_ctc_score", ptr(acts), ptr(input_lengths), ptr(lexicon) if lexicon.numel() else ptr(lexicon_lengths), ptr(lexicon_lengths),
+         K if per_sample else 0, C, N, T, K, Lmax, blank, ptr(costs), ptr(best), ptr(best_cost), ptr(log_norm), ptr(workspace),
+         workspace.numel(), _st())
+    return costs, best, best_cost, log_norm
+
+
 def ctc_greedy_decode(acts, input_lengths, blank=0, pad_value=0):
     T, N, C = acts.shape
     out = torch.empty((N, T), dtype=torch.int32, device=acts.device)
