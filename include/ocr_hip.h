@@ -33,6 +33,8 @@ int ocr_abi_version(void);
 const char* ocr_build_id(void);
 
 /* ---- CTC (replaces warpctc_tensorflow.ctc, network.py:653-654; warp-ctc get_workspace_size/compute_ctc_loss) */
+/* ctc.hip: the general one-wave kernel and the fast kernel (S = 2L+1 <= 64, tables in LDS); every CTC kernel derives its sample's label
+ * offset itself, no scan launch */
 int ocr_ctc_workspace_size(int max_label_len, int max_time, int minibatch, size_t* bytes);
 /* activations/gradients: f32 [max_time, minibatch, alphabet_size], unnormalised; gradients may be NULL (score only).
  * flat_labels / label_lengths / input_lengths are DEVICE int32 arrays (warp-ctc's GPU path takes them from the host;
@@ -42,14 +44,15 @@ int ocr_ctc_loss(const float* activations, float* gradients, const int* flat_lab
                  int blank_label, float* costs, void* workspace, void* stream);
 /* training form: one launch producing costs and scale * gradient as bf16 [minibatch][max_time][alphabet] (what the backward
  * GEMMs read); label offsets computed in-kernel.  ocr_ctc_train_supported() == 0 -> use ocr_ctc_loss + ocr_tnc_to_ntc_bf16 */
-/* diagnostic: device int64[5] receiving 100 MHz wall-clock stamps at the phase boundaries of sample 0 of the fast kernel (NULL = off) */
+/* diagnostic: device int64[5] receiving 100 MHz wall-clock stamps at the phase boundaries of sample 0 of the fast kernel (NULL = off);
+ * the stamps are compiled only into the experiments build (make EXPERIMENTS=1), the product library stores the pointer and never reads it */
 int ocr_ctc_debug(void* dbg);
 int ocr_ctc_train_supported(int alphabet_size, int max_time, int max_label_len);
 int ocr_ctc_loss_train(const float* activations, void* grad_ntc_bf16, float scale, const int* flat_labels,
                        const int* label_lengths, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
                        int max_label_len, int blank_label, float* costs, void* stream);
 int ocr_set_ctc_engine(int fast);   /* 1 (default): 4-wave LDS-resident kernel where it fits; 0: one-wave general kernel */
-/* long labels, 1 <= max_label_len <= 255 (S = 2L+1 <= 511): one launch, one 16-wave workgroup per sample, 2 / 4 / 8 extended-label slots
+/* ctc_long.hip.  Long labels, 1 <= max_label_len <= 255 (S = 2L+1 <= 511): one launch, one 16-wave workgroup per sample, 2 / 4 / 8 extended-label slots
  * per lane.  Same semantics as ocr_ctc_loss; label offsets computed in-kernel.  Writes the f32 [T][N][C] gradient, the bf16 [N][T][C]
  * gradient multiplied by `scale`, both, or neither (score only).  The [T][S] tables live in LDS when they fit and in `workspace`
  * otherwise: ocr_ctc_long_placement = 0 not covered, 1 LDS, 2 workspace (arithmetic only); ocr_ctc_long_workspace_size gives 0 bytes for

@@ -158,14 +158,14 @@ def declared_symbols(header=HEADER_PATH):
 
 
 def source_build_id(csrc=os.path.join(_HERE, "csrc"), experiments=False):
-    """The id `make` compiles into the library (csrc/Makefile: sha256 over the sorted sources, common.h, conv_plan.h and the Makefile,
+    """The id `make` compiles into the library (csrc/Makefile: sha256 over the sorted sources, common.h, conv_plan.h, ctc_common.h and the Makefile,
     16 hex digits; the experiments flavour adds the suffix '-exp'), recomputed from the source tree: equal to build_id() unless the .so
     is stale."""
     import glob
     import hashlib
     rel = [os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*.hip"))]
     h = hashlib.sha256()
-    for f in sorted(rel) + ["common.h", "conv_plan.h", "Makefile"]:          # make's $(sort ...) orders the same byte-wise way
+    for f in sorted(rel) + ["common.h", "conv_plan.h", "ctc_common.h", "Makefile"]:          # make's $(sort ...) orders the same byte-wise way
         h.update(open(os.path.join(csrc, f), "rb").read())
     return h.hexdigest()[:16] + ("-exp" if experiments else "")
 

@@ -16,7 +16,7 @@
 //                            log sum_k exp(-cost) (-inf when none is finite).
 // Infeasible means +inf, never 0: Tn <= 0, L + repeats > Tn, L outside [0, max_label_len], or a label inside the candidate's length that is
 // outside [0, C) or equals the blank.  Such a label is never used as an index, and words beyond a candidate's length are never read.
-#include "common.h"
+#include "ctc_common.h"
 #include <math.h>
 
 constexpr int SCORE_MAX_C = 16384;
@@ -26,22 +26,12 @@ constexpr int SCORE_PER = 16;            // row elements a thread of the rows ke
 constexpr int SCORE_WAVE_ROW_C = 64 * SCORE_PER;      // up to here a row fits one wave
 constexpr int SCORE_CW = 4;              // candidates (waves) per workgroup of the candidates kernel
 
-// log(e^a + e^b + e^c) as straight-line code on v_exp_f32 / v_log_f32 (ctc.hip's lse3_flat): with every input -inf the maximum is replaced by 0,
-// the sum is 0 and the logarithm -inf, so no branch sits on the chain
-__device__ __forceinline__ float score_lse3(float a, float b, float c) {
-    const float m = fmaxf(fmaxf(a, b), c);
-    const float m0 = (m == NEG_INF) ? 0.f : m;
-    constexpr float LOG2E = 1.44269504088896341f, LN2 = 0.693147180559945309f;
-    const float sum = __builtin_amdgcn_exp2f((a - m0) * LOG2E) + __builtin_amdgcn_exp2f((b - m0) * LOG2E) + __builtin_amdgcn_exp2f((c - m0) * LOG2E);
-    return m0 + __builtin_amdgcn_logf(sum) * LN2;
-}
-
 // TPR threads hold one row: TPR == NT (one row per workgroup, two barriers) or TPR == 64 (one row per wave, NT / 64 rows per workgroup).
-// VEC consecutive elements per load: 8 / 4 need C % VEC == 0 and a 16-byte aligned tensor.
+// The row is loaded and reduced by ctc_common.h's row-in-registers helpers.
 template <int NT, int TPR, int VEC>
 __global__ __launch_bounds__(NT) void ctc_score_rows_kernel(const float* __restrict__ act, const int* __restrict__ input_len, int T, int N, int C,
                                                             float* __restrict__ lse_out) {
-    constexpr int RPB = NT / TPR, NCH = SCORE_PER / VEC, NW = TPR / 64;
+    constexpr int RPB = NT / TPR, NW = TPR / 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long r = (long)blockIdx.x * RPB + (RPB > 1 ? wave : 0);
     const int rt = RPB > 1 ? lane : tid;                  // thread within the row
@@ -51,42 +41,13 @@ __global__ __launch_bounds__(NT) void ctc_score_rows_kernel(const float* __restr
     const float* row = act + (size_t)r * C;
 
     float v[SCORE_PER];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int k = (i * TPR + rt) * VEC;
-        const bool in = k < C;                            // (covers k + VEC <= C: C is a multiple of VEC)
-        if constexpr (VEC == 1) v[i] = in ? row[k] : NEG_INF;
-        else {
-#pragma unroll
-            for (int q = 0; q < VEC / 4; ++q) {
-                const f32x4 x = in ? *(const f32x4*)(row + k + 4 * q) : (f32x4){NEG_INF, NEG_INF, NEG_INF, NEG_INF};
-                v[i * VEC + 4 * q] = x.x; v[i * VEC + 4 * q + 1] = x.y; v[i * VEC + 4 * q + 2] = x.z; v[i * VEC + 4 * q + 3] = x.w;
-            }
-        }
-    }
-    float m = v[0];
-#pragma unroll
-    for (int j = 1; j < SCORE_PER; ++j) m = fmaxf(m, v[j]);
-    m = wave_max(m);
-    __shared__ float s_max[NW > 1 ? NW : 1], s_sum[NW > 1 ? NW : 1];
-    if constexpr (NW > 1) {
-        if (lane == 0) s_max[wave] = m;
-        __syncthreads();
-        m = s_max[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) m = fmaxf(m, s_max[w]);
-    }
+    ctc_load_row<TPR, VEC>(row, C, rt, true, v);
+    __shared__ float s_max[NW > 1 ? NW : 1], s_sum[NW > 1 ? NW : 1];          // (untouched by the one-wave-per-row form: no LDS, no barrier)
+    const float m = ctc_row_max<NW>(v, s_max, lane, wave);
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < SCORE_PER; ++j) sum += __expf(v[j] - m);          // (elements past C: exp(-inf) = 0)
-    sum = wave_sum(sum);
-    if constexpr (NW > 1) {
-        if (lane == 0) s_sum[wave] = sum;
-        __syncthreads();
-        sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) sum += s_sum[w];
-    }
+    sum = ctc_row_sum<NW>(sum, s_sum, lane, wave);
     if (rt == 0) lse_out[r] = m + logf(sum);
 }
 
@@ -163,7 +124,7 @@ __global__ __launch_bounds__(64 * SCORE_CW) void ctc_score_cands_kernel(
         for (int v = 0; v < VT; ++v) {
             const float x1 = v >= 1 ? a[v >= 1 ? v - 1 : 0] : p1;
             const float x2 = v >= 2 ? a[v >= 2 ? v - 2 : 0] : (v == 1 ? p1 : p2);
-            na[v] = score_lse3(a[v], x1, skip[v] ? x2 : NEG_INF) + ly[v];
+            na[v] = lse3_flat(a[v], x1, skip[v] ? x2 : NEG_INF) + ly[v];
         }
 #pragma unroll
         for (int v = 0; v < VT; ++v) a[v] = na[v];
@@ -171,14 +132,8 @@ __global__ __launch_bounds__(64 * SCORE_CW) void ctc_score_cands_kernel(
     }
 #undef SCORE_LOAD
 #undef SCORE_LOGY
-    float x1 = NEG_INF, x2 = NEG_INF;
-#pragma unroll
-    for (int v = 0; v < VT; ++v) {
-        if (v == ((S - 1) & (VT - 1))) x1 = a[v];
-        if (S >= 2 && v == ((S - 2) & (VT - 1))) x2 = a[v];
-    }
-    const float e1 = __shfl(x1, (S - 1) / VT, 64);
-    const float e2 = (S >= 2) ? __shfl(x2, (S - 2) / VT, 64) : NEG_INF;
+    float e1, e2;
+    ctc_last_two<VT>(a, S, e1, e2);
     if (lane == 0) {
         const float m = fmaxf(e1, e2);
         *out = (m == NEG_INF) ? INFINITY : -(m + logf(expf(e1 - m) + expf(e2 - m)));
@@ -239,7 +194,7 @@ extern "C" int ocr_ctc_score_supported(int alphabet_size, int max_time, int max_
 extern "C" int ocr_ctc_score_workspace_size(int alphabet_size, int max_time, int minibatch, size_t* bytes) {
     if (!bytes || minibatch <= 0 || !ocr_ctc_score_supported(alphabet_size, max_time, 0, 1) || (long)minibatch * max_time > 0x7fffffffL)
         return OCR_ERR_INVALID;
-    *bytes = ((size_t)minibatch * max_time * sizeof(float) + 255) & ~(size_t)255;
+    *bytes = ctc_align256((size_t)minibatch * max_time * sizeof(float));
     return OCR_OK;
 }
 template <int NT, int TPR, int VEC>
@@ -279,7 +234,7 @@ extern "C" int ocr_ctc_score(const float* activations, const int* input_lengths,
     OCR_CHECK_LAUNCH();
 
     const dim3 grid(ceil_div(K, SCORE_CW), N);
-    const int SMAX = 2 * max_label_len + 1;
+    const int SMAX = smax_for(max_label_len);
 #define SCORE_CANDS(V)                                                                                                            \
     ctc_score_cands_kernel<V><<<grid, 64 * SCORE_CW, 0, stream>>>(activations, lse, input_lengths, cand_labels, cand_lengths, sample_stride, T, N, C, K, \
                                                                   max_label_len, blank_label, costs)

@@ -1,19 +1,11 @@
-// warp-ctc's C ABI (include/warpctc_abi.h) over the gfx950 CTC kernels of ctc.hip.
+// warp-ctc's C ABI (include/warpctc_abi.h) over the gfx950 CTC kernels of ctc.hip and ctc_long.hip.
 // Replaces libwarpctc behind `warpctc_tensorflow.ctc` (reference lib/networks/network.py:6,653-654): host label / length
 // arrays and host costs as in warp-ctc's GPU path; they are staged through the caller's workspace, so the library still
 // allocates nothing and keeps no state.
 #include "common.h"
+#include "../../include/ocr_hip.h"
 #include "../../include/warpctc_abi.h"
 #include <algorithm>
-
-extern "C" int ocr_ctc_workspace_size(int max_label_len, int max_time, int minibatch, size_t* bytes);
-extern "C" int ocr_ctc_loss(const float* activations, float* gradients, const int* flat_labels, const int* label_lengths,
-                            const int* input_lengths, int alphabet_size, int minibatch, int max_time, int max_label_len,
-                            int blank_label, float* costs, void* workspace, void* stream);
-extern "C" int ocr_ctc_long_workspace_size(int alphabet_size, int max_label_len, int max_time, int minibatch, size_t* bytes);
-extern "C" int ocr_ctc_loss_long(const float* activations, float* gradients, void* grad_ntc_bf16, float scale, const int* flat_labels,
-                                 const int* label_lengths, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
-                                 int max_label_len, int blank_label, float* costs, void* workspace, size_t workspace_bytes, void* stream);
 
 namespace {
 struct Extents { int max_t, max_l; long total_l; bool ok; };

@@ -133,13 +133,8 @@ class ShapePlan(object):
             self.buf['wgrad_ws'] = torch.empty(need, dtype=torch.uint8, device=dev)
         self.T, _, self.C = self.oshape[eng.ops[-1].key]
         self.costs = torch.zeros(N, dtype=F32, device=dev)
-        path = eng.ctc_path_of(self.C, self.T)
-        self.ctc_grad = torch.empty((self.T, N, self.C) if path != 'wide' else (0,), dtype=F32, device=dev)    # (the wide form has no f32 hand-off)
-        ws_bytes = ops.ctc_workspace_bytes(eng.max_label_len, self.T, N) if eng.max_label_len <= 127 else 1      # (the general kernel stops at 127)
-        if path == 'long':
-            ws_bytes = max(ws_bytes, ops.ctc_long_workspace_bytes(self.C, eng.max_label_len, self.T, N))
-        elif path == 'wide':
-            ws_bytes = ops.ctc_wide_workspace_bytes(self.C, eng.max_label_len, self.T, N)
+        _, ws_bytes, grad_shape = eng.ctc_form_of(self.C, self.T, N)
+        self.ctc_grad = torch.empty(grad_shape, dtype=F32, device=dev)
         self.ctc_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         self.decoded = torch.zeros((N, self.T), dtype=I32, device=dev)
         self.decoded_len = torch.zeros(N, dtype=I32, device=dev)
@@ -534,7 +529,7 @@ class Engine(object):
         logits = self.ops[-1].y(sp)
         # loss = mean over the GLOBAL batch -> d loss / d cost_n = 1 / (N * world)   (network.py:655)
         scale = ocr_dist.loss_scale(sp.N, self.world)
-        path = self.ctc_path_of(sp.C, sp.T)
+        path = self.ctc_form_of(sp.C, sp.T, sp.N)[0]
         if path == 'fast':
             ops.ctc_loss_train(logits, self.ops[-1].dy(sp), scale, sp.labels, sp.labels_len, sp.seq_len, self.max_label_len,
                                sp.costs, blank=0)
@@ -561,7 +556,7 @@ class Engine(object):
     def ctc_path_of(self, C, T):
         """Which CTC form a plan with T frames of C classes takes: 'fast' (ctc_fast_kernel's training form, S <= 64 with its tables in
         LDS), 'long' (ctc_long_kernel, one launch, labels up to 255), 'wide' (rows kernel + samples kernel, up to 16384 classes: only the
-        shapes neither of those two kernels covers) or 'general' (scan + one-wave kernel + transpose)."""
+        shapes neither of those two kernels covers) or 'general' (one-wave kernel + transpose)."""
         if ops.ctc_train_supported(C, T, self.max_label_len):
             return 'fast'
         long_covers = ops.ctc_long_supported(C, T, self.max_label_len)
@@ -570,6 +565,18 @@ class Engine(object):
         if self.ctc_wide and not long_covers and ops.ctc_wide_supported(C, T, self.max_label_len):
             return 'wide'
         return 'general'
+
+    def ctc_form_of(self, C, T, N):
+        """-> (path, workspace bytes, shape of the f32 gradient hand-off) of a plan with N samples of T frames of C classes: everything a
+        plan allocates for its CTC loss and the step dispatches on."""
+        path = self.ctc_path_of(C, T)
+        if path == 'wide':          # no f32 hand-off: both of its kernels write the bf16 gradient themselves
+            return path, ops.ctc_wide_workspace_bytes(C, self.max_label_len, T, N), (0,)
+        # every other plan keeps the general kernel's workspace where that kernel covers the labels (it stops at 127 characters)
+        ws_bytes = ops.ctc_workspace_bytes(self.max_label_len, T, N) if self.max_label_len <= 127 else 1
+        if path == 'long':
+            ws_bytes = max(ws_bytes, ops.ctc_long_workspace_bytes(C, self.max_label_len, T, N))
+        return path, ws_bytes, (T, N, C)
 
     def ctc_path(self, N, W):
         sp = self.plan(N, W)

@@ -74,21 +74,29 @@ def ctc_long_workspace_bytes(C, max_label_len, max_time, minibatch):
     return sz.value
 
 
-def ctc_loss_long(acts, labels, label_lengths, input_lengths, max_label_len, blank=0, want_grad=True, grad_ntc_bf16=None, scale=1.0,
-                  workspace=None, costs=None, grads=None):
-    """Labels of up to 255 characters in one launch: costs, the f32 [T, N, C] gradient (want_grad) and / or scale * gradient as bf16
-    [N, T, C] (grad_ntc_bf16).  -> (costs, f32 gradient or None)."""
+def _ctc_loss_tables(entry, workspace_bytes, acts, labels, label_lengths, input_lengths, max_label_len, blank, want_grad, grad_ntc_bf16, scale,
+                     workspace, costs, grads):
+    """The long-label and wide-alphabet forms: one signature, `entry` the C entry point and `workspace_bytes` its size function (0 for the
+    long form with its tables in LDS: one byte is allocated then; the wide form's is never 0)."""
     T, N, C = acts.shape
     _dev(acts)
     if workspace is None:
-        workspace = torch.empty(max(ctc_long_workspace_bytes(C, max_label_len, T, N), 1), dtype=torch.uint8, device=acts.device)
+        workspace = torch.empty(max(workspace_bytes(C, max_label_len, T, N), 1), dtype=torch.uint8, device=acts.device)
     if costs is None:
         costs = torch.empty(N, dtype=F32, device=acts.device)
     if want_grad and grads is None:
         grads = torch.empty_like(acts)
-    call("ocr_ctc_loss_long", ptr(acts), ptr(grads) if want_grad else None, ptr(grad_ntc_bf16), float(scale), ptr(labels),
+    call(entry, ptr(acts), ptr(grads) if want_grad else None, ptr(grad_ntc_bf16), float(scale), ptr(labels),
          ptr(label_lengths), ptr(input_lengths), C, N, T, max_label_len, blank, ptr(costs), ptr(workspace), workspace.numel(), _st())
     return costs, (grads if want_grad else None)
+
+
+def ctc_loss_long(acts, labels, label_lengths, input_lengths, max_label_len, blank=0, want_grad=True, grad_ntc_bf16=None, scale=1.0,
+                  workspace=None, costs=None, grads=None):
+    """Labels of up to 255 characters in one launch: costs, the f32 [T, N, C] gradient (want_grad) and / or scale * gradient as bf16
+    [N, T, C] (grad_ntc_bf16).  -> (costs, f32 gradient or None)."""
+    return _ctc_loss_tables("ocr_ctc_loss_long", ctc_long_workspace_bytes, acts, labels, label_lengths, input_lengths, max_label_len, blank,
+                            want_grad, grad_ntc_bf16, scale, workspace, costs, grads)
 
 
 def ctc_wide_supported(C, T, max_label_len):
@@ -106,17 +114,8 @@ def ctc_loss_wide(acts, labels, label_lengths, input_lengths, max_label_len, bla
                   workspace=None, costs=None, grads=None):
     """Wide alphabets (up to 16384 classes) in two launches, one workgroup per logit row and one per sample: costs, the f32 [T, N, C]
     gradient (want_grad) and / or scale * gradient as bf16 [N, T, C] (grad_ntc_bf16).  -> (costs, f32 gradient or None)."""
-    T, N, C = acts.shape
-    _dev(acts)
-    if workspace is None:
-        workspace = torch.empty(ctc_wide_workspace_bytes(C, max_label_len, T, N), dtype=torch.uint8, device=acts.device)
-    if costs is None:
-        costs = torch.empty(N, dtype=F32, device=acts.device)
-    if want_grad and grads is None:
-        grads = torch.empty_like(acts)
-    call("ocr_ctc_loss_wide", ptr(acts), ptr(grads) if want_grad else None, ptr(grad_ntc_bf16), float(scale), ptr(labels),
-         ptr(label_lengths), ptr(input_lengths), C, N, T, max_label_len, blank, ptr(costs), ptr(workspace), workspace.numel(), _st())
-    return costs, (grads if want_grad else None)
+    return _ctc_loss_tables("ocr_ctc_loss_wide", ctc_wide_workspace_bytes, acts, labels, label_lengths, input_lengths, max_label_len, blank,
+                            want_grad, grad_ntc_bf16, scale, workspace, costs, grads)
 
 
 def ctc_score_supported(C, T, max_label_len, K):

@@ -1,4 +1,4 @@
-"""Cases, float32 model and bounds of the long-label CTC kernel (ctc.hip: ctc_long_kernel).  A helper module, not collected.
+"""Cases, float32 model and bounds of the long-label CTC kernel (ctc_long.hip: ctc_long_kernel).  A helper module, not collected.
 
 Reference: the float64 oracle (oracle/ctc.py::ctc_loss_numpy).  Bounds, by the rule of tests/test_gpu_ctc_trained.py: the kernels' recursion in
 numpy float32 (that file's ctc_recursion) against the oracle gives the floor that float32 log-space arithmetic has of its own on these inputs,

@@ -1,4 +1,4 @@
-"""Cases, bounds and host arithmetic of the wide-alphabet CTC loss (ctc.hip: ctc_wide_rows_kernel + ctc_wide_samples_kernel).  A helper module,
+"""Cases, bounds and host arithmetic of the wide-alphabet CTC loss (ctc_long.hip: ctc_wide_rows_kernel + ctc_wide_samples_kernel).  A helper module,
 not collected; the Case class, the float32 model and the oracle are those of tests/ctc_long_cases.py.
 
 Reference: the float64 oracle (oracle/ctc.py::ctc_loss_numpy).  Bounds, by the rule of tests/test_gpu_ctc_trained.py: the kernels' recursion in

@@ -1,4 +1,4 @@
-"""-m gpu: the long-label CTC kernel (ctc.hip: ctc_long_kernel, ops.ctc_loss_long) against the float64 oracle on the cases of
+"""-m gpu: the long-label CTC kernel (ctc_long.hip: ctc_long_kernel, ops.ctc_loss_long) against the float64 oracle on the cases of
 tests/ctc_long_cases.py, its refusals, and the engine's choice of it.  Bounds and their derivation: ctc_long_cases.py.
 
 Measured on an MI355X (worst over the 15 cases and the four forms; the test prints every figure before it asserts):

@@ -1,4 +1,4 @@
-"""CTC (ctc.hip) where the product trains: on the TRAINED logits of the committed fixture, and on the boundary shapes of the fast kernel.
+"""CTC (ctc.hip, ctc_common.h) where the product trains: on the TRAINED logits of the committed fixture, and on the boundary shapes of the fast kernel.
 
 Trained logits (tests/golden/trained_expect.npz, all five batches; labels and lengths from captcha_batches.npz).  A trained network's
 cost per sample is 9e-5 .. 6e-2 (median 3.5e-4) and its largest gradient entry 0.012 .. 0.06, so the bounds of the random-logit cases

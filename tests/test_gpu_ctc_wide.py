@@ -1,4 +1,4 @@
-"""-m gpu: the wide-alphabet CTC loss (ctc.hip: ctc_wide_rows_kernel + ctc_wide_samples_kernel, ops.ctc_loss_wide) against the float64 oracle
+"""-m gpu: the wide-alphabet CTC loss (ctc_long.hip: ctc_wide_rows_kernel + ctc_wide_samples_kernel, ops.ctc_loss_wide) against the float64 oracle
 on the cases of tests/ctc_wide_cases.py, on small-alphabet cases of tests/ctc_long_cases.py, its refusals, and the engine's choice of it.
 Bounds and their derivation: ctc_wide_cases.py (ctc_long_cases.py for its own cases).
 

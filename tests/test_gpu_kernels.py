@@ -213,6 +213,10 @@ def test_ctc_edge_cases(dev):
     # non-zero blank
     _ctc_case(dev, 20, 4, 10, [3, 4, 5, 2], [20, 18, 15, 9], 7, blank=9,
               labels=[[1, 2, 3], [0, 0, 4, 8], [5, 6, 7, 8, 0], [2, 2]])
+    # ragged batch of more samples than a wave has lanes: the general kernel's 64-lane strided sum of the label lengths in front of a
+    # sample (its label offset) takes a second trip; 21 empty labels, 11 infeasible samples, 59 feasible ones
+    rng = np.random.RandomState(21)
+    _ctc_case(dev, 12, 70, 8, rng.randint(0, 5, 70).tolist(), rng.randint(1, 13, 70).tolist(), 9)
 
 
 def test_ctc_greedy(dev):

@@ -1,4 +1,5 @@
-"""Phase breakdown of the fast CTC kernel (diagnostic)."""
+"""Phase breakdown of the fast CTC kernel (diagnostic).  The stamps are compiled only into the experiments build (`make EXPERIMENTS=1`): run with
+OCR_NATIVE_LIB=.../lstm_ctc_ocr_amd/libocrhip_exp.so; the product library stores the pointer and never writes a stamp."""
 import os, sys, ctypes, torch, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lstm_ctc_ocr_amd import ops, _native as nat

@@ -1,4 +1,4 @@
-"""CTC loss + bf16 training-form gradient at wide alphabets: the general path (exclusive_scan_small + ctc_loss_grad_kernel + ocr_tnc_to_ntc_bf16
+"""CTC loss + bf16 training-form gradient at wide alphabets: the general path (ctc_loss_grad_kernel + ocr_tnc_to_ntc_bf16
 over a float32 [T][N][C] scratch) against the wide path (ctc_wide_rows_kernel + ctc_wide_samples_kernel), in one process, as alternating pairs
 of timed windows.  Prints every window, the range of each path per shape, and the bytes the wide path's launches move (from the shapes).
     python tools/ctc_wide_bench.py [--pairs 3] [--reps 20] [--shapes '6625,64,63,25;...']
