@@ -101,6 +101,41 @@ int ocr_ctc_score_workspace_size(int alphabet_size, int max_time, int minibatch,
 int ocr_ctc_score(const float* activations, const int* input_lengths, const int* cand_labels, const int* cand_lengths, int sample_stride,
                   int alphabet_size, int minibatch, int max_time, int num_candidates, int max_label_len, int blank_label,
                   float* costs, int* best, float* best_cost, float* log_norm, void* workspace, size_t workspace_bytes, void* stream);
+/* lexicon scoring on a prefix tree: the costs, best, best_cost and log_norm of ocr_ctc_score for ONE lexicon shared by every sample, of up to
+ * 1048576 words (ocr_ctc_trie_supported: 1 <= alphabet_size <= 16384, max_time >= 1, 1 <= num_words <= 1048576; arithmetic only).  Every node
+ * of the lexicon's prefix tree runs the alpha recursion of its label slot and of the blank slot behind it once, whatever the number of words
+ * below it, so the work is max_time x nodes instead of max_time x sum(2 L + 1).
+ * ocr_ctc_trie_build (host code, no GPU) turns a dense lexicon (words int32 [num_words][max_label_len], lengths int32 [num_words], the layout
+ * of ocr_ctc_score) into a CHUNKED tree: the words are sorted lexicographically and the sorted order is cut into contiguous ranges whose own
+ * tries have at most chunk_nodes nodes each, the root and the ancestors shared with a neighbouring range included (a chunk is one workgroup's
+ * work; ocr_ctc_trie_chunk_capacity() = 8192 is the most a workgroup holds).  Two passes: with nodes == NULL it writes only *num_chunks and
+ * *num_nodes; with the five arrays given, and *num_chunks / *num_nodes holding what the arrays were sized for, it fills
+ *   nodes            : int32 [*num_nodes], chunk after chunk.  A record = label | parent << 14 | flag << 27: parent is the index within the
+ *                      chunk (parent < child; node 0 of a chunk is the root, label = blank_label, its own parent), flag = the node may take its
+ *                      parent's non-blank mass (its label differs from the parent's);
+ *   chunk_node_start : int32 [*num_chunks + 1], chunk_word_start: int32 [*num_chunks + 1]: prefix sums over nodes and over sorted words;
+ *   word_node        : int32 [num_words], per word in sorted order its terminal node within its chunk; word_index: int32 [num_words], its index
+ *                      in the caller's order.  Equal words share a node.  A word ocr_ctc_score would price +inf for every sample (a length
+ *                      outside [0, max_label_len] or above 255, a label inside the length outside [0, alphabet_size) or equal to the blank) is
+ *                      never inserted: node -1, in chunk 0.  Words at or beyond a word's length are never read.
+ * OCR_ERR_INVALID for num_words < 1 or above 1048576, chunk_nodes below (longest valid word + 1) or above the capacity, a blank outside
+ * [0, alphabet_size), NULL operands, or arrays too small.
+ * ocr_ctc_score_trie: three launches on `stream` (log-sum-exp rows into `workspace`, ocr_ctc_trie_workspace_size bytes; one workgroup per
+ * (chunk, sample); arg-min and normaliser), no host synchronisation.  The arrays are device copies of the builder's, chunk_nodes an upper bound
+ * of every chunk's node count (the value the tree was built with).  costs f32 [minibatch][num_words] in the caller's word order, +inf as
+ * ocr_ctc_score defines it; best / best_cost / log_norm as there, NULL together to skip the third launch.  OCR_ERR_INVALID, with nothing
+ * launched, for a NULL operand, partly NULL outputs, a blank outside [0, alphabet_size), a short workspace, chunk_nodes outside
+ * [1, capacity], num_chunks outside [1, num_words + 1], minibatch > 65535, or a shape ocr_ctc_trie_supported refuses. */
+int ocr_ctc_trie_chunk_capacity(void);
+int ocr_ctc_trie_supported(int alphabet_size, int max_time, int num_words);
+int ocr_ctc_trie_build(const int* words, const int* lengths, int num_words, int max_label_len, int alphabet_size, int blank_label,
+                       int chunk_nodes, int* num_chunks, int* num_nodes, int* nodes, int* chunk_node_start, int* chunk_word_start,
+                       int* word_node, int* word_index);
+int ocr_ctc_trie_workspace_size(int alphabet_size, int max_time, int minibatch, size_t* bytes);
+int ocr_ctc_score_trie(const float* activations, const int* input_lengths, const int* nodes, const int* chunk_node_start,
+                       const int* chunk_word_start, const int* word_node, const int* word_index, int num_chunks, int chunk_nodes,
+                       int alphabet_size, int minibatch, int max_time, int num_words, int blank_label, float* costs, int* best,
+                       float* best_cost, float* log_norm, void* workspace, size_t workspace_bytes, void* stream);
 /* best-path decode (argmax, collapse repeats, drop blank): the greedy counterpart of
  * tf.nn.ctc_beam_search_decoder + sparse_tensor_to_dense(default 0) at network.py:656-657 / test.py:30-31.
  * decoded: int32 [minibatch, max_time] padded with pad_value; decoded_lengths: int32 [minibatch]. */

@@ -37,7 +37,12 @@ _SIGS = {
     "ocr_ctc_score_supported": ([_I, _I, _I, _I], _I),
     "ocr_ctc_score_workspace_size": ([_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_score": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
-    "ocr_ctc_greedy_decode": ([_P, _P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
+    "ocr_ctc_trie_chunk_capacity": ([], _I),
+    "ocr_ctc_trie_supported": ([_I, _I, _I], _I),
+    "ocr_ctc_trie_build": ([_P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _P, _P, _P, _P], _I),
+    "ocr_ctc_trie_workspace_size": ([_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
+    "ocr_ctc_score_trie": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "ocr_ctc_greedy_decode":([_P, _P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "ocr_ctc_beam_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_beam_decode": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "ocr_ctc_beam_kernel_choice": ([_I, _I], _I),

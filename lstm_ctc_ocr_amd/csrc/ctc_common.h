@@ -1,4 +1,4 @@
-// What the CTC sources (ctc.hip, ctc_long.hip, ctc_score.hip) share: the log-add-exp forms, a sample's set-up, the frame-parallel pieces of the
+// What the CTC sources (ctc.hip, ctc_long.hip, ctc_score.hip, ctc_trie.hip) share: the log-add-exp forms, a sample's set-up, the frame-parallel pieces of the
 // loss kernels (row log-sum-exp, zero-fill, posterior accumulation, gradient-row store), the row-in-registers loader of the chip-wide rows
 // kernels, and the host-side sizes more than one file needs.
 #pragma once
@@ -175,4 +175,109 @@ static inline bool ctc_loss_args_ok(const float* activations, const int* flat_la
                                     const float* costs, int alphabet_size, int minibatch, int max_time, int max_label_len, int blank_label) {
     return activations && flat_labels && label_lengths && input_lengths && costs && alphabet_size > 0 && minibatch > 0 && max_time > 0 &&
            max_label_len >= 0 && blank_label >= 0 && blank_label < alphabet_size;
+}
+
+// ---- what the lexicon scorers (ctc_score.hip per candidate, ctc_trie.hip per prefix-tree node) share: the lse[t][n] rows launch and the
+// arg-min / log-normaliser launch.  Kernels and launchers are templates (the launchers' parameter has no other use) so that only the sources
+// that launch them instantiate them: the other CTC objects stay what they were.
+constexpr int SCORE_MAX_C = 16384;
+constexpr int SCORE_PER = 16;            // row elements a thread of the rows kernel keeps
+constexpr int SCORE_WAVE_ROW_C = 64 * SCORE_PER;      // up to here a row fits one wave
+
+// TPR threads hold one row: TPR == NT (one row per workgroup, two barriers) or TPR == 64 (one row per wave, NT / 64 rows per workgroup).
+// The row is loaded and reduced by ctc_common.h's row-in-registers helpers.
+template <int NT, int TPR, int VEC>
+__global__ __launch_bounds__(NT) void ctc_score_rows_kernel(const float* __restrict__ act, const int* __restrict__ input_len, int T, int N, int C,
+                                                            float* __restrict__ lse_out) {
+    constexpr int RPB = NT / TPR, NW = TPR / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long r = (long)blockIdx.x * RPB + (RPB > 1 ? wave : 0);
+    const int rt = RPB > 1 ? lane : tid;                  // thread within the row
+    if (r >= (long)T * N) return;                         // (per wave when RPB > 1, per workgroup otherwise: no barrier is skipped by a part)
+    const int t = (int)(r / N), n = (int)(r - (long)t * N);
+    if (t >= min(input_len[n], T)) return;                // not a frame of this sample: neither read nor written
+    const float* row = act + (size_t)r * C;
+
+    float v[SCORE_PER];
+    ctc_load_row<TPR, VEC>(row, C, rt, true, v);
+    __shared__ float s_max[NW > 1 ? NW : 1], s_sum[NW > 1 ? NW : 1];          // (untouched by the one-wave-per-row form: no LDS, no barrier)
+    const float m = ctc_row_max<NW>(v, s_max, lane, wave);
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < SCORE_PER; ++j) sum += __expf(v[j] - m);          // (elements past C: exp(-inf) = 0)
+    sum = ctc_row_sum<NW>(sum, s_sum, lane, wave);
+    if (rt == 0) lse_out[r] = m + logf(sum);
+}
+
+template <int NT, int TPR, int VEC>
+static void ctc_score_rows_launch(const float* act, const int* il, int T, int N, int C, float* lse, hipStream_t stream) {
+    const long rows = (long)T * N;
+    ctc_score_rows_kernel<NT, TPR, VEC><<<ceil_div(rows, NT / TPR), NT, 0, stream>>>(act, il, T, N, C, lse);
+}
+// the rows launch of the lexicon scorers: a wave per row while a wave's registers hold it (no barrier, four rows per workgroup); else the
+// smallest workgroup that holds the row.  The caller checks the launch.
+template <int INSTANCE = 0>
+static inline void ctc_score_rows(const float* activations, const int* input_lengths, int T, int N, int C, float* lse, hipStream_t stream) {
+    const bool al16 = ((uintptr_t)activations & 15) == 0;
+    const int VEC = (al16 && C % 8 == 0) ? 8 : (al16 && C % 4 == 0) ? 4 : 1;
+#define SCORE_ROWS(NT, TPR)                                                                       \
+    do {                                                                                          \
+        if (VEC == 8) ctc_score_rows_launch<NT, TPR, 8>(activations, input_lengths, T, N, C, lse, stream);       \
+        else if (VEC == 4) ctc_score_rows_launch<NT, TPR, 4>(activations, input_lengths, T, N, C, lse, stream);  \
+        else ctc_score_rows_launch<NT, TPR, 1>(activations, input_lengths, T, N, C, lse, stream);                \
+    } while (0)
+    if (C <= SCORE_WAVE_ROW_C) SCORE_ROWS(256, 64);
+    else if (C <= 256 * SCORE_PER) SCORE_ROWS(256, 256);
+    else if (C <= 512 * SCORE_PER) SCORE_ROWS(512, 512);
+    else SCORE_ROWS(1024, 1024);
+#undef SCORE_ROWS
+}
+
+constexpr int SCORE_BEST_NT = 256;
+template <int INSTANCE = 0>
+__global__ __launch_bounds__(SCORE_BEST_NT) void ctc_score_best_kernel(const float* __restrict__ costs, int K, int* __restrict__ best,
+                                                                       float* __restrict__ best_cost, float* __restrict__ log_norm) {
+    constexpr int NW = SCORE_BEST_NT / 64;
+    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* c_n = costs + (size_t)n * K;
+    __shared__ float s_c[NW], s_sum[NW];
+    __shared__ int s_i[NW];
+    float bc = INFINITY;
+    int bi = 0x7fffffff;
+    for (int k = tid; k < K; k += SCORE_BEST_NT) {
+        const float c = c_n[k];
+        if (c < bc) { bc = c; bi = k; }                   // (ascending k per thread: strict < keeps the lowest index)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float oc = __shfl_xor(bc, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (oc < bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
+    }
+    if (lane == 0) { s_c[wave] = bc; s_i[wave] = bi; }
+    __syncthreads();
+    bc = s_c[0]; bi = s_i[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w)
+        if (s_c[w] < bc || (s_c[w] == bc && s_i[w] < bi)) { bc = s_c[w]; bi = s_i[w]; }
+    const bool any = bc < INFINITY;
+    float sum = 0.f;
+    if (any)
+        for (int k = tid; k < K; k += SCORE_BEST_NT) sum += expf(bc - c_n[k]);          // (+inf cost: exp(-inf) = 0)
+    sum = wave_sum(sum);
+    if (lane == 0) s_sum[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) sum += s_sum[w];
+        best[n] = any ? bi : -1;
+        best_cost[n] = bc;
+        log_norm[n] = any ? logf(sum) - bc : NEG_INF;
+    }
+}
+
+template <int INSTANCE = 0>
+static inline void ctc_score_best(const float* costs, int N, int K, int* best, float* best_cost, float* log_norm, hipStream_t stream) {
+    ctc_score_best_kernel<INSTANCE><<<N, SCORE_BEST_NT, 0, stream>>>(costs, K, best, best_cost, log_norm);
 }

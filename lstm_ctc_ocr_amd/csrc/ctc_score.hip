@@ -3,7 +3,8 @@
 // of ctc.hip take one label per sample (K candidates would mean K copies of the logits) and report an infeasible label as cost 0, which would
 // win every arg-min; here an impossible candidate costs +inf.
 //
-// Three launches, ordered by the stream (no workgroup waits on another):
+// Three launches, ordered by the stream (no workgroup waits on another); the first and the last are shared with ctc_trie.hip and live in
+// ctc_common.h:
 //   ctc_score_rows_kernel    lse[t][n] = log sum_c exp(act[t][n][c]) for the rows a sample owns (t < Tn), the row held in registers (16 elements a
 //                            thread, as ctc_wide_rows_kernel): one workgroup of 256 / 512 / 1024 threads per row, or, for C <= 1024, one WAVE per
 //                            row and four rows per workgroup (no LDS, no barrier).  Rows with t >= Tn are neither read nor written.
@@ -19,37 +20,9 @@
 #include "ctc_common.h"
 #include <math.h>
 
-constexpr int SCORE_MAX_C = 16384;
 constexpr int SCORE_MAX_LABEL = 255;
 constexpr int SCORE_MAX_K = 65536;
-constexpr int SCORE_PER = 16;            // row elements a thread of the rows kernel keeps
-constexpr int SCORE_WAVE_ROW_C = 64 * SCORE_PER;      // up to here a row fits one wave
 constexpr int SCORE_CW = 4;              // candidates (waves) per workgroup of the candidates kernel
-
-// TPR threads hold one row: TPR == NT (one row per workgroup, two barriers) or TPR == 64 (one row per wave, NT / 64 rows per workgroup).
-// The row is loaded and reduced by ctc_common.h's row-in-registers helpers.
-template <int NT, int TPR, int VEC>
-__global__ __launch_bounds__(NT) void ctc_score_rows_kernel(const float* __restrict__ act, const int* __restrict__ input_len, int T, int N, int C,
-                                                            float* __restrict__ lse_out) {
-    constexpr int RPB = NT / TPR, NW = TPR / 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long r = (long)blockIdx.x * RPB + (RPB > 1 ? wave : 0);
-    const int rt = RPB > 1 ? lane : tid;                  // thread within the row
-    if (r >= (long)T * N) return;                         // (per wave when RPB > 1, per workgroup otherwise: no barrier is skipped by a part)
-    const int t = (int)(r / N), n = (int)(r - (long)t * N);
-    if (t >= min(input_len[n], T)) return;                // not a frame of this sample: neither read nor written
-    const float* row = act + (size_t)r * C;
-
-    float v[SCORE_PER];
-    ctc_load_row<TPR, VEC>(row, C, rt, true, v);
-    __shared__ float s_max[NW > 1 ? NW : 1], s_sum[NW > 1 ? NW : 1];          // (untouched by the one-wave-per-row form: no LDS, no barrier)
-    const float m = ctc_row_max<NW>(v, s_max, lane, wave);
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < SCORE_PER; ++j) sum += __expf(v[j] - m);          // (elements past C: exp(-inf) = 0)
-    sum = ctc_row_sum<NW>(sum, s_sum, lane, wave);
-    if (rt == 0) lse_out[r] = m + logf(sum);
-}
 
 // VT = extended-label slots per lane (S = 2L+1 <= 64 * VT for every L <= max_label_len: chosen on the host)
 template <int VT>
@@ -140,49 +113,6 @@ __global__ __launch_bounds__(64 * SCORE_CW) void ctc_score_cands_kernel(
     }
 }
 
-constexpr int SCORE_BEST_NT = 256;
-__global__ __launch_bounds__(SCORE_BEST_NT) void ctc_score_best_kernel(const float* __restrict__ costs, int K, int* __restrict__ best,
-                                                                       float* __restrict__ best_cost, float* __restrict__ log_norm) {
-    constexpr int NW = SCORE_BEST_NT / 64;
-    const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* c_n = costs + (size_t)n * K;
-    __shared__ float s_c[NW], s_sum[NW];
-    __shared__ int s_i[NW];
-    float bc = INFINITY;
-    int bi = 0x7fffffff;
-    for (int k = tid; k < K; k += SCORE_BEST_NT) {
-        const float c = c_n[k];
-        if (c < bc) { bc = c; bi = k; }                   // (ascending k per thread: strict < keeps the lowest index)
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float oc = __shfl_xor(bc, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oc < bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
-    }
-    if (lane == 0) { s_c[wave] = bc; s_i[wave] = bi; }
-    __syncthreads();
-    bc = s_c[0]; bi = s_i[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w)
-        if (s_c[w] < bc || (s_c[w] == bc && s_i[w] < bi)) { bc = s_c[w]; bi = s_i[w]; }
-    const bool any = bc < INFINITY;
-    float sum = 0.f;
-    if (any)
-        for (int k = tid; k < K; k += SCORE_BEST_NT) sum += expf(bc - c_n[k]);          // (+inf cost: exp(-inf) = 0)
-    sum = wave_sum(sum);
-    if (lane == 0) s_sum[wave] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        sum = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) sum += s_sum[w];
-        best[n] = any ? bi : -1;
-        best_cost[n] = bc;
-        log_norm[n] = any ? logf(sum) - bc : NEG_INF;
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // C ABI (declared in include/ocr_hip.h)
 // ------------------------------------------------------------------------------------------
@@ -196,11 +126,6 @@ extern "C" int ocr_ctc_score_workspace_size(int alphabet_size, int max_time, int
         return OCR_ERR_INVALID;
     *bytes = ctc_align256((size_t)minibatch * max_time * sizeof(float));
     return OCR_OK;
-}
-template <int NT, int TPR, int VEC>
-static void ctc_score_rows_launch(const float* act, const int* il, int T, int N, int C, float* lse, hipStream_t stream) {
-    const long rows = (long)T * N;
-    ctc_score_rows_kernel<NT, TPR, VEC><<<ceil_div(rows, NT / TPR), NT, 0, stream>>>(act, il, T, N, C, lse);
 }
 extern "C" int ocr_ctc_score(const float* activations, const int* input_lengths, const int* cand_labels, const int* cand_lengths, int sample_stride,
                              int alphabet_size, int minibatch, int max_time, int num_candidates, int max_label_len, int blank_label, float* costs,
@@ -217,20 +142,7 @@ extern "C" int ocr_ctc_score(const float* activations, const int* input_lengths,
     const int C = alphabet_size, N = minibatch, T = max_time, K = num_candidates;
     float* lse = (float*)workspace;
 
-    const bool al16 = ((uintptr_t)activations & 15) == 0;
-    const int VEC = (al16 && C % 8 == 0) ? 8 : (al16 && C % 4 == 0) ? 4 : 1;
-#define SCORE_ROWS(NT, TPR)                                                                       \
-    do {                                                                                          \
-        if (VEC == 8) ctc_score_rows_launch<NT, TPR, 8>(activations, input_lengths, T, N, C, lse, stream);       \
-        else if (VEC == 4) ctc_score_rows_launch<NT, TPR, 4>(activations, input_lengths, T, N, C, lse, stream);  \
-        else ctc_score_rows_launch<NT, TPR, 1>(activations, input_lengths, T, N, C, lse, stream);                \
-    } while (0)
-    // a wave per row while a wave's registers hold it (no barrier, four rows per workgroup); else the smallest workgroup that holds the row
-    if (C <= SCORE_WAVE_ROW_C) SCORE_ROWS(256, 64);
-    else if (C <= 256 * SCORE_PER) SCORE_ROWS(256, 256);
-    else if (C <= 512 * SCORE_PER) SCORE_ROWS(512, 512);
-    else SCORE_ROWS(1024, 1024);
-#undef SCORE_ROWS
+    ctc_score_rows(activations, input_lengths, T, N, C, lse, stream);
     OCR_CHECK_LAUNCH();
 
     const dim3 grid(ceil_div(K, SCORE_CW), N);
@@ -243,7 +155,7 @@ extern "C" int ocr_ctc_score(const float* activations, const int* input_lengths,
     OCR_CHECK_LAUNCH();
 
     if (outs == 3) {
-        ctc_score_best_kernel<<<N, SCORE_BEST_NT, 0, stream>>>(costs, K, best, best_cost, log_norm);
+        ctc_score_best(costs, N, K, best, best_cost, log_norm, stream);
         OCR_CHECK_LAUNCH();
     }
     return OCR_OK;

@@ -25,6 +25,7 @@ from . import ops
 from ._native import NativeError, call as nat_call
 from .engine_ops import (BF16, F32, I32, _env, _number, _switch, _AddOp, _AvgPoolOp, _BatchNormOp, _BiLstmOp, _ConcatOp, _ConvOp,
                          _Conv3x3Op, _DropoutOp, _FcOp, _InputOp, _PoolOp, _ReluOp, _SoftmaxOp, _SubsampleOp, _ViewOp, _conv_op)
+from .lexicon import LexiconTrie
 from .layout import FlatLayout, execution_order, init_host_parameters
 
 ALIGN = 64               # parameter offsets are multiples of 64 elements (256 B)
@@ -846,10 +847,14 @@ class Engine(object):
                           blank is class C-1; class 0 is an ordinary symbol that sparse_to_dense/ignore_value=0 strip later
                           (network.py:656-657, training.py:32).
         method='greedy' : best path with blank 0.
-        method='lexicon': the likeliest string of `lexicon` (label lists, blank 0) under CTC; [] for a sample none of them fits."""
+        method='lexicon': the likeliest string of `lexicon` (label lists, blank 0, or a lexicon.LexiconTrie built with blank 0) under CTC; [] for a
+                          sample none of them fits.  With a LexiconTrie only the arg-min leaves the device, not the N x K cost matrix."""
         if method == 'lexicon':
             if lexicon is None:
                 raise ValueError("decode(method='lexicon') needs a lexicon")
+            if isinstance(lexicon, LexiconTrie):
+                best = self._score_trie(data, seq_len, lexicon, 0)[1].cpu().numpy()
+                return [[int(v) for v in lexicon[b] if v != 0] if b >= 0 else [] for b in best]
             _, best, _, _ = self.score(data, seq_len, lexicon, blank=0)
             return [[int(v) for v in lexicon[b] if v != 0] if b >= 0 else [] for b in best]
         sp = self.plan(data.shape[0], data.shape[1])
@@ -883,11 +888,23 @@ class Engine(object):
         self._lexicon = (lexicon, labels, lengths)
         return labels, lengths
 
+    def _score_trie(self, data, seq_len, trie, blank):
+        """Device costs, best, best_cost, log_norm of a LexiconTrie from one forward pass."""
+        if blank != trie.blank:
+            raise ValueError('blank %d, but the LexiconTrie was built with blank %d' % (blank, trie.blank))
+        sp = self.plan(data.shape[0], data.shape[1])
+        self._bind(sp, data, seq_len)
+        self._run(sp, 'fwd')
+        return ops.ctc_score_trie(self.ops[-1].y(sp), sp.seq_len, trie)
+
     def score(self, data, seq_len, lexicon, blank=0):
         """CTC costs of every string of `lexicon` (a list of label lists in the training convention: blank 0, classes from 1) for every sample,
         from one forward pass: -> (costs [N, K] float32, +inf for a string the sample cannot emit; best [N] int32, -1 where none can;
         best_cost [N]; log_norm [N] = log sum_k exp(-costs)) as numpy arrays.  exp(-costs - log_norm[:, None]) is the posterior within
-        the lexicon."""
+        the lexicon.  A lexicon.LexiconTrie in place of the list takes the prefix-tree route (ops.ctc_score_trie: up to 1048576 words, shared prefixes
+        computed once); its blank must be `blank`.  A list always takes the per-candidate route."""
+        if isinstance(lexicon, LexiconTrie):
+            return tuple(v.cpu().numpy() for v in self._score_trie(data, seq_len, lexicon, blank))
         labels, lengths = self._pack_lexicon(lexicon)
         sp = self.plan(data.shape[0], data.shape[1])
         self._bind(sp, data, seq_len)

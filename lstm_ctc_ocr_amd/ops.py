@@ -158,6 +158,41 @@ def ctc_score(acts, input_lengths, lexicon, lexicon_lengths, blank=0, per_sample
     return costs, best, best_cost, log_norm
 
 
+def ctc_trie_supported(C, T, K):
+    """C <= 16384 classes, a lexicon of up to 1048576 words (host arithmetic only)."""
+    return bool(nat.lib().ocr_ctc_trie_supported(C, T, K))
+
+
+def ctc_trie_workspace_bytes(C, max_time, minibatch):
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_trie_workspace_size", C, max_time, minibatch, ctypes.byref(sz))
+    return sz.value
+
+
+def ctc_score_trie(acts, input_lengths, trie, workspace=None, costs=None, want_best=True):
+    """ctc_score for a lexicon.LexiconTrie (one lexicon shared by the samples, its blank and class count the trie's): every node of the prefix
+    tree runs its recursion once.  -> (costs [N, K] f32 in the trie's original word order, best, best_cost, log_norm) as ctc_score.  The first
+    call on a device copies the trie's arrays there (trie.device_arrays(device) does it ahead of a graph capture); later calls only launch."""
+    T, N, C = acts.shape
+    _dev(acts)
+    if C != trie.num_classes:
+        raise ValueError('logits of %d classes, a LexiconTrie built for %d' % (C, trie.num_classes))
+    K = trie.num_words
+    arrays = trie.device_arrays(acts.device)
+    if workspace is None:
+        workspace = torch.empty(ctc_trie_workspace_bytes(C, T, N), dtype=torch.uint8, device=acts.device)
+    if costs is None:
+        costs = torch.empty((N, K), dtype=F32, device=acts.device)
+    best = best_cost = log_norm = None
+    if want_best:
+        best = torch.empty(N, dtype=torch.int32, device=acts.device)
+        best_cost = torch.empty(N, dtype=F32, device=acts.device)
+        log_norm = torch.empty(N, dtype=F32, device=acts.device)
+    call("ocr_ctc_score_trie", ptr(acts), ptr(input_lengths), *[ptr(a) for a in arrays], trie.num_chunks, trie.chunk_nodes, C, N, T, K, trie.blank,
+         ptr(costs), ptr(best), ptr(best_cost), ptr(log_norm), ptr(workspace), workspace.numel(), _st())
+    return costs, best, best_cost, log_norm
+
+
 def ctc_greedy_decode(acts, input_lengths, blank=0, pad_value=0):
     T, N, C = acts.shape
     out = torch.empty((N, T), dtype=torch.int32, device=acts.device)
