@@ -194,6 +194,7 @@ class Engine(object):
         self.comm_stream = torch.cuda.Stream(device=self.device)
         self.dp_host_s = [0.0, 0.0, 0.0, 0.0, 0.0, 0]      # host enqueue seconds of the data-parallel schedule's phases + step count (train_step)
         self._pack_table = None                          # built by the first refresh_weights
+        self._pack_table_host = None                     # its host copy (numpy PACK_DTYPE records)
         self._fault_hook = None                          # fault injection (tests): called with the plan in front of the drop-flag launch
         self._watch_pending = None                       # the watchdog's outstanding report (_watchdog)
         self.dropped_reports = 0                         # steps whose update the device dropped, as seen by report_wait
@@ -304,34 +305,105 @@ class Engine(object):
     def _build_pack_table(self):
         # plain bf16 copies only of the variables some op reads through Engine.shadow (the 3x3 convolution weights — most of the
         # parameters — have their own packed layouts): a flat shadow of everything was 28 MB read + 14 MB written per step
-        jobs = []
+        jobs, labels = [], []
         for op in self.ops:
             for name in op.shadow_params():
                 n = int(np.prod(self.specs[name].shape))
-                assert n % 4 == 0, name
                 jobs.append(dict(type=3, src=self._view(self.params, name).reshape(-1), dst=self._view(self.params_bf16, name).reshape(-1), n=n))
+                labels.append('bf16 shadow of ' + name)
         for op in self.ops:
-            jobs.extend(op.pack_jobs())
-        tab = np.zeros(len(jobs), self.PACK_DTYPE)
+            mine = op.pack_jobs()
+            jobs.extend(mine)
+            labels.extend([op.name] * len(mine))
+        tab, blocks = self.pack_table(jobs)
+        self.validate_pack_table(tab, blocks, labels)
+        self._pack_table_host = tab                      # (the host copy: what the tests compare the operands' byte ranges with)
+        self._pack_table = torch.from_numpy(tab.view(np.uint8).copy()).to(self.device)
+        self._pack_njobs, self._pack_blocks = len(jobs), blocks
+
+    @staticmethod
+    def pack_job_blocks(j):
+        """Workgroups a pack job (a dict as op.pack_jobs() returns it) gets: one per 64 x 64 tile of a transpose, else one per 256 work
+        items up to a cap (the kernel's loops stride by the job's block count)."""
+        t = j['type']
+        if t == 0:
+            return ((j['Cc'] + 63) // 64) * ((j['R'] + 63) // 64)
+        if t == 1:
+            return min((j['n'] + 255) // 256, 512)
+        if t == 2:
+            return min((j['R'] * j['Cc'] // 4 + 255) // 256, 512)
+        if t == 4:
+            return min((j['n'] + 255) // 256, 512)
+        return min((j['n'] // 4 + 255) // 256, 2048)
+
+    @staticmethod
+    def pack_table(jobs):
+        """Job dicts (src / dst: tensors or device addresses) -> (PACK_DTYPE records in the given order, total workgroups).  Pure host."""
+        addr = lambda a: a.data_ptr() if hasattr(a, 'data_ptr') else int(a)
+        tab = np.zeros(len(jobs), Engine.PACK_DTYPE)
         start = 0
         for i, j in enumerate(jobs):
-            t = j['type']
-            if t == 0:
-                nb = ((j['Cc'] + 63) // 64) * ((j['R'] + 63) // 64)
-            elif t == 1:
-                nb = min((j['n'] + 255) // 256, 512)
-            elif t == 2:
-                nb = min((j['R'] * j['Cc'] // 4 + 255) // 256, 512)
-            elif t == 4:
-                nb = min((j['n'] + 255) // 256, 512)
-            else:
-                nb = min((j['n'] // 4 + 255) // 256, 2048)
-            tab[i] = (t, j.get('R', 0), j.get('Cc', 0), j.get('lstm_units', 0), j.get('ldin', 0), j.get('ldout', 0),
-                      j['src'].data_ptr(), j['dst'].data_ptr(), j.get('n', 0), start, nb)
+            nb = Engine.pack_job_blocks(j)
+            tab[i] = (j['type'], j.get('R', 0), j.get('Cc', 0), j.get('lstm_units', 0), j.get('ldin', 0), j.get('ldout', 0),
+                      addr(j['src']), addr(j['dst']), j.get('n', 0), start, nb)
             start += nb
-        assert tab.itemsize == 64
-        self._pack_table = torch.from_numpy(tab.view(np.uint8).copy()).to(self.device)
-        self._pack_njobs, self._pack_blocks = len(jobs), start
+        return tab, start
+
+    @staticmethod
+    def validate_pack_table(tab, total_blocks, labels=None):
+        """What pack_jobs_kernel (csrc/stream_ops.hip) takes for granted about its table, checked on the host copy (ocr_pack_jobs sees only a
+        device pointer).  Raises ValueError naming the job (and labels[job], where given) and the rule; every rule is a line of the kernel:
+          the job search  takes the last job whose block_start <= blockIdx.x and b = blockIdx.x - block_start: block_start must be the running
+                          sum of nblocks from 0, every nblocks >= 1 (a job without blocks is never found), and the launch has total_blocks blocks;
+          type 0          one block per 64 x 64 tile, b -> (b % ctiles, b / ctiles): fewer blocks than tiles leave tiles stale; reads
+                          src[r * ldin + c], 16 bytes at once where ldin % 4 == 0; writes dst[perm(c) * R + r], 8 bytes at once where R % 4 == 0;
+                          perm(c) = (u / 16) * 64 + g * 16 + u % 16 stays inside [0, Cc) only for Cc == 4 U and U % 16 == 0;
+          type 1          four output channels per thread: n / 4 float4s of w[tap][ci][co], tap = idx / (Cout / 4) / Cin must stay below 9;
+          type 2, 3       float4 loads and 8-byte stores only, no scalar path: every count and stride is a multiple of 4;
+          type 4          out[perm(i)] = src[i] for i < n, fp32 to fp32.
+        The grid-stride types (1 - 4) are correct for any nblocks >= 1."""
+        if tab.dtype != Engine.PACK_DTYPE:
+            raise ValueError('pack table: dtype is not Engine.PACK_DTYPE')
+        if len(tab) < 1:
+            raise ValueError('pack table: no jobs')
+        start = 0
+        for i, j in enumerate(tab):
+            t = int(j['type'])
+            R, Cc, U, ldin, ldout, n = (int(j[k]) for k in ('R', 'Cc', 'lstm_units', 'ldin', 'ldout', 'n'))
+            src, dst, nb = int(j['src']), int(j['dst']), int(j['nblocks'])
+
+            def need(ok, rule):
+                if not ok:
+                    raise ValueError('pack job %d (type %d)%s: %s' % (i, t, ' of ' + labels[i] if labels else '', rule))
+            need(0 <= t <= 4, 'type is one of 0 .. 4')
+            need(nb >= 1, 'nblocks >= 1')
+            need(int(j['block_start']) == start, 'block_start is the running sum of nblocks')
+            need(src != 0 and dst != 0, 'src and dst are non-null')
+            src_align, dst_align = 16, 8
+            if t == 0:
+                need(R >= 1 and Cc >= 1, 'R, Cc >= 1')
+                need(ldin >= Cc, 'ldin >= Cc')
+                need(nb == ((Cc + 63) // 64) * ((R + 63) // 64), 'nblocks is the number of 64 x 64 tiles')
+                if U > 0:
+                    need(Cc == 4 * U and U % 16 == 0, 'Cc == 4 * lstm_units and lstm_units % 16 == 0')
+                src_align = 16 if (ldin % 4 == 0 and Cc >= 4) else 4
+                dst_align = 8 if R % 4 == 0 else 2
+            elif t == 1:
+                need(R >= 1 and Cc >= 4 and Cc % 4 == 0, 'Cin >= 1, Cout >= 4 and Cout % 4 == 0')
+                need(n == 9 * R * Cc, 'n == 9 * Cin * Cout')
+            elif t == 2:
+                need(R >= 1 and Cc >= 4 and Cc % 4 == 0 and ldin % 4 == 0 and ldout % 4 == 0, 'Cc, ldin and ldout are multiples of 4')
+                need(ldin >= Cc and ldout >= Cc, 'ldin >= Cc and ldout >= Cc')
+            elif t == 3:
+                need(n >= 4 and n % 4 == 0, 'n % 4 == 0 and n >= 4')
+            else:
+                need(U >= 16 and U % 16 == 0 and n == 4 * U, 'n == 4 * lstm_units and lstm_units % 16 == 0')
+                src_align = dst_align = 4
+            need(src % src_align == 0, 'src is %d-byte aligned' % src_align)
+            need(dst % dst_align == 0, 'dst is %d-byte aligned' % dst_align)
+            start += nb
+        if start != int(total_blocks):
+            raise ValueError('pack table: total_blocks %d is not the sum of nblocks %d' % (int(total_blocks), start))
 
     def refresh_weights(self):
         if self._pack_table is None:

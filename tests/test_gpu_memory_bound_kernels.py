@@ -11,6 +11,8 @@ Selections, copies, integer outputs and bf16 values produced by an exact rule ar
 derived in a comment from the operation's rounding and quotes the worst error measured on the MI355X.
 """
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -19,8 +21,11 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from lstm_ctc_ocr_amd import ops
-from oracle import plan_exec
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from pack_model import EDGE, EDGE_BITS, _plain_randoms  # noqa: E402,F401
+
+from lstm_ctc_ocr_amd import ops  # noqa: E402
+from oracle import plan_exec  # noqa: E402
 
 BF = torch.bfloat16
 WG = 256                # threads per workgroup of every kernel below but softmax (64: one wave per row)
@@ -558,33 +563,7 @@ def test_dropout_mask_is_the_oracles(dev, regime, keep_prob):
 
 
 # ================================================================================================ casts (stream_ops.hip)
-EDGE_BITS = [
-    0x00000000, 0x80000000,                          # +-0
-    0x00000001, 0x80000001,                          # smallest denormals: round to +-0
-    0x00008000, 0x00018000,                          # denormal ties: to even (stays 0) and from odd (up to 0x0002)
-    0x00400000, 0x00410000,                          # denormals bf16 holds exactly
-    0x007f8000,                                      # denormal tie from odd: rounds up to the smallest bf16 normal 0x0080
-    0x007fffff, 0x807fffff,                          # largest denormals: round to +-0x0080, a normal
-    0x00800000,                                      # smallest normal
-    0x3f808000, 0xbf808000,                          # ties with an even lower half: stay
-    0x3f818000, 0xbf818000,                          # ties with an odd lower half: go up
-    0x3f808001, 0x3f807fff,                          # just above / below a tie
-    0x7f7f7fff, 0xff7f7fff,                          # largest floats that round to +-bf16 max 0x7f7f
-    0x7f7f8000, 0xff7f8000,                          # smallest floats that round to +-Inf
-    0x7f7fffff,                                      # FLT_MAX -> Inf
-    0x7f800000, 0xff800000,                          # +-Inf
-    0x7fc00000, 0xffc00000, 0x7fc12345,              # quiet NaNs, one with a payload
-    0x7f800001, 0xff800001, 0x7fa00000, 0x7f80ffff,  # signalling NaNs, payloads in the low half only: truncation would give +-Inf
-]
-EDGE = torch.from_numpy(np.array(EDGE_BITS, dtype=np.uint32).view(np.float32).copy())
-
-
-def _plain_randoms(n, seed):
-    """Uniform values in [-1, 1] and, every other element, uniform fp32 bit patterns (every exponent, some NaNs)."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.rand(n, generator=g) * 2 - 1
-    x[1::2] = torch.randint(-2 ** 31, 2 ** 31, (len(range(1, n, 2)),), dtype=torch.int64, generator=g).to(torch.int32).view(torch.float32)
-    return x
+# EDGE_BITS, EDGE and _plain_randoms: tests/pack_model.py (shared with the weight re-pack tests)
 
 
 def _assert_bf16_rule(what, got, src):
