@@ -136,6 +136,25 @@ int ocr_ctc_score_trie(const float* activations, const int* input_lengths, const
                        const int* chunk_word_start, const int* word_node, const int* word_index, int num_chunks, int chunk_nodes,
                        int alphabet_size, int minibatch, int max_time, int num_words, int blank_label, float* costs, int* best,
                        float* best_cost, float* log_norm, void* workspace, size_t workspace_bytes, void* stream);
+/* ctc_topk.hip.  The k best of a lexicon: for every row n of costs (f32, N rows of K entries, row stride ld >= K floats, any 4-byte aligned
+ * base: a row-strided view of a larger matrix is fine) the k entries that are smallest under the total order "cost as a float, -0.0 == +0.0,
+ * then the lower index", ascending.  +inf entries are never returned; NaN is outside the contract (the scorers produce none).
+ * 1 <= k <= 64, 1 <= K <= 1048576 (ocr_ctc_topk_supported: arithmetic only), 1 <= N <= 65535.
+ *   index    : int32 [N][k]; cost: f32 [N][k], the selected entries' own bits (signed zeros as stored); count: int32 [N] = min(k, finite entries
+ *              of the row).  Slots at and beyond count[n] hold index -1, cost +inf, log_post -inf.
+ *   log_post : f32 [N][k] = (-cost) - log_norm[n] (one fp32 negate and one subtract), or NULL.  log_norm: f32 [N] (what ocr_ctc_score writes), may
+ *              be NULL; then log_post must be NULL too.
+ * ocr_ctc_topk_plan (host only) reports how the launch cuts a row: `segments` pieces of `segment_len` entries (the last one shorter), a
+ * workgroup per (segment, sample); one segment for rows of up to 8192 entries and wherever N alone fills the chip.  With more than one segment
+ * a second launch merges the segments' k keys from `workspace` (ocr_ctc_topk_workspace_size bytes, 8-byte aligned; 0 bytes for a one-segment
+ * plan, `workspace` may then be NULL).  The result is fully determined (no atomics, no dependence on workgroup order).  ocr_ctc_topk only
+ * launches: no allocation, no synchronisation, no host read of device memory.  OCR_ERR_INVALID, with nothing launched, for a NULL costs /
+ * index / cost / count, log_post without log_norm, ld < K, a short or missing workspace, or N, K, k out of range. */
+int ocr_ctc_topk_supported(int K, int k);
+int ocr_ctc_topk_plan(int N, int K, int k, int* segments, int* segment_len);
+int ocr_ctc_topk_workspace_size(int N, int K, int k, size_t* bytes);
+int ocr_ctc_topk(const float* costs, long ld, int N, int K, int k, const float* log_norm, int* index, float* cost, float* log_post,
+                 int* count, void* workspace, size_t workspace_bytes, void* stream);
 /* best-path decode (argmax, collapse repeats, drop blank): the greedy counterpart of
  * tf.nn.ctc_beam_search_decoder + sparse_tensor_to_dense(default 0) at network.py:656-657 / test.py:30-31.
  * decoded: int32 [minibatch, max_time] padded with pad_value; decoded_lengths: int32 [minibatch]. */

@@ -42,6 +42,10 @@ _SIGS = {
     "ocr_ctc_trie_build": ([_P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _P, _P, _P, _P], _I),
     "ocr_ctc_trie_workspace_size": ([_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_score_trie": ([_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "ocr_ctc_topk_supported": ([_I, _I], _I),
+    "ocr_ctc_topk_plan": ([_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
+    "ocr_ctc_topk_workspace_size": ([_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
+    "ocr_ctc_topk": ([_P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "ocr_ctc_greedy_decode":([_P, _P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "ocr_ctc_beam_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_beam_decode": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),

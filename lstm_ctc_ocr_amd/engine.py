@@ -975,14 +975,33 @@ class Engine(object):
         best_cost [N]; log_norm [N] = log sum_k exp(-costs)) as numpy arrays.  exp(-costs - log_norm[:, None]) is the posterior within
         the lexicon.  A lexicon.LexiconTrie in place of the list takes the prefix-tree route (ops.ctc_score_trie: up to 1048576 words, shared prefixes
         computed once); its blank must be `blank`.  A list always takes the per-candidate route."""
+        return tuple(v.cpu().numpy() for v in self._score_device(data, seq_len, lexicon, blank))
+
+    def _score_device(self, data, seq_len, lexicon, blank):
+        """score's four results as device tensors: the prefix-tree route for a LexiconTrie, the per-candidate route for a list."""
         if isinstance(lexicon, LexiconTrie):
-            return tuple(v.cpu().numpy() for v in self._score_trie(data, seq_len, lexicon, blank))
+            return self._score_trie(data, seq_len, lexicon, blank)
         labels, lengths = self._pack_lexicon(lexicon)
         sp = self.plan(data.shape[0], data.shape[1])
         self._bind(sp, data, seq_len)
         self._run(sp, 'fwd')
-        logits = self.ops[-1].y(sp)
-        return tuple(v.cpu().numpy() for v in ops.ctc_score(logits, sp.seq_len, labels, lengths, blank=blank))
+        return ops.ctc_score(self.ops[-1].y(sp), sp.seq_len, labels, lengths, blank=blank)
+
+    def nbest(self, data, seq_len, lexicon, k=5, blank=0):
+        """The k likeliest strings of `lexicon` (a list of label lists or a lexicon.LexiconTrie, as score takes them) for every sample, from one
+        forward pass: -> (index [N, k] int32 into the lexicon, best first; costs [N, k] float32; log_post [N, k] float32 = -costs - log_norm, the
+        log-posterior within the lexicon; count [N] int32 = how many of the k slots hold a string the sample can emit) as numpy arrays.  Slots at
+        and beyond count[n] hold -1 / +inf / -inf.  Ties go to the lower index.  The selection runs on the device (ops.ctc_topk): only these
+        O(N k) values leave it, not the N x K cost matrix."""
+        costs, _, _, log_norm = self._score_device(data, seq_len, lexicon, blank)
+        return tuple(v.cpu().numpy() for v in ops.ctc_topk(costs, k, log_norm=log_norm))
+
+    def decode_nbest(self, data, seq_len, lexicon, k=5):
+        """decode(method='lexicon') with alternatives: per sample a list of count[n] <= k pairs (labels with zeros dropped, log-posterior within the
+        lexicon), best first; [] for a sample none of the lexicon's strings fits.  The lexicon's blank is 0, as decode's."""
+        index, _, log_post, count = self.nbest(data, seq_len, lexicon, k=k, blank=0)
+        return [[([int(v) for v in lexicon[int(index[n, j])] if v != 0], float(log_post[n, j])) for j in range(int(count[n]))]
+                for n in range(index.shape[0])]
 
     def setup_optimizer(self, solver=None, lr=None):
         c = self.cfg.TRAIN

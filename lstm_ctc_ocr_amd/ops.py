@@ -193,6 +193,54 @@ def ctc_score_trie(acts, input_lengths, trie, workspace=None, costs=None, want_b
     return costs, best, best_cost, log_norm
 
 
+def ctc_topk_supported(K, k):
+    """Rows of up to 1048576 entries, the 1 .. 64 best of each (host arithmetic only)."""
+    return bool(nat.lib().ocr_ctc_topk_supported(K, k))
+
+
+def ctc_topk_plan(N, K, k):
+    """-> (segments, segment_len): how ctc_topk cuts a row of K entries at N samples, a workgroup per (segment, sample); host arithmetic only."""
+    if not ctc_topk_supported(K, k):
+        raise ValueError('ctc_topk takes 1 <= K <= 1048576 entries and 1 <= k <= 64 (got K = %d, k = %d)' % (K, k))
+    segments, segment_len = ctypes.c_int(0), ctypes.c_int(0)
+    call("ocr_ctc_topk_plan", N, K, k, ctypes.byref(segments), ctypes.byref(segment_len))
+    return segments.value, segment_len.value
+
+
+def ctc_topk_workspace_bytes(N, K, k):
+    if not ctc_topk_supported(K, k):
+        raise ValueError('ctc_topk takes 1 <= K <= 1048576 entries and 1 <= k <= 64 (got K = %d, k = %d)' % (K, k))
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_topk_workspace_size", N, K, k, ctypes.byref(sz))
+    return sz.value
+
+
+def ctc_topk(costs, k, log_norm=None, workspace=None):
+    """The k smallest entries of every row of costs (f32 [N, K]; a view with a row stride is taken as it is, its columns must be contiguous) under
+    the total order (cost with -0.0 == +0.0, then the lower index), ascending; +inf entries are never returned.
+    -> (index [N, k] i32, cost [N, k] f32 with the entries' own bits, log_post [N, k] f32 = (-cost) - log_norm[n] or None without log_norm,
+    count [N] i32); slots at and beyond count[n] hold -1 / +inf / -inf."""
+    _dev(costs)
+    if costs.dim() != 2 or costs.dtype != F32 or (costs.shape[1] > 1 and costs.stride(1) != 1) or (costs.shape[0] > 1 and costs.stride(0) < costs.shape[1]):
+        raise ValueError('ctc_topk takes a float32 [N, K] matrix whose rows are contiguous (got %s %s, strides %s)'
+                         % (costs.dtype, tuple(costs.shape), tuple(costs.stride())))
+    N, K = int(costs.shape[0]), int(costs.shape[1])
+    k = int(k)
+    need = ctc_topk_workspace_bytes(N, K, k)               # (ValueError for a K or k outside the limits)
+    ld = int(costs.stride(0)) if N > 1 else K
+    if log_norm is not None and (log_norm.dtype != F32 or log_norm.numel() != N or not log_norm.is_contiguous()):
+        raise ValueError('log_norm must be a contiguous float32 [N]')
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=costs.device)
+    index = torch.empty((N, k), dtype=torch.int32, device=costs.device)
+    cost = torch.empty((N, k), dtype=F32, device=costs.device)
+    count = torch.empty(N, dtype=torch.int32, device=costs.device)
+    log_post = torch.empty((N, k), dtype=F32, device=costs.device) if log_norm is not None else None
+    call("ocr_ctc_topk", ptr(costs), ld, N, K, k, ptr(log_norm), ptr(index), ptr(cost), ptr(log_post), ptr(count), ptr(workspace),
+         workspace.numel(), _st())
+    return index, cost, log_post, count
+
+
 def ctc_greedy_decode(acts, input_lengths, blank=0, pad_value=0):
     T, N, C = acts.shape
     out = torch.empty((N, T), dtype=torch.int32, device=acts.device)
