@@ -155,6 +155,25 @@ int ocr_ctc_topk_plan(int N, int K, int k, int* segments, int* segment_len);
 int ocr_ctc_topk_workspace_size(int N, int K, int k, size_t* bytes);
 int ocr_ctc_topk(const float* costs, long ld, int N, int K, int k, const float* log_norm, int* index, float* cost, float* log_post,
                  int* count, void* workspace, size_t workspace_bytes, void* stream);
+/* ctc_align.hip.  Forced alignment: the best (Viterbi) alignment of every candidate against the logits, with the operands, limits and the
+ * meaning of "cannot be emitted" of ocr_ctc_score (num_candidates = 1 with sample_stride = 1 aligns each sample to its own transcript).
+ *   start, end : int32 [minibatch][num_candidates][max_label_len], the first and last frame (inclusive, inside [0, input length)) the best
+ *                path spends on character j; score: f32, same shape, the sum over those frames of act[t][n][label_j] - lse[t][n] added in
+ *                ascending t; path_cost: f32 [minibatch][num_candidates], minus the log-probability of the best path.
+ *   A candidate that cannot be emitted gets -1 / -1 / -inf in all max_label_len slots and path_cost +inf; one that can gets -1 / -1 / -inf in
+ *   the slots at and beyond its length.  Length 0 is the all-blank path: no spans.
+ * The recursion is max-plus in fp32 on ly = act - lse (no exp, no log): v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if the skip is
+ * allowed) + ly; of equal values the smaller step wins (stay, then one slot, then two); the path ends in the last slot unless the one before
+ * it is strictly better.  Two launches on `stream`: the log-sum-exp rows into the head of `workspace` (as ocr_ctc_score), then one wave per
+ * (sample, candidate).  ocr_ctc_align_workspace_size: the lse table plus, when max_time > 64, 128 bytes per (sample, candidate, frame) of
+ * back-pointers; OCR_ERR_INVALID above 2^40 bytes.  Every output word is written exactly once per call; no atomics.
+ * OCR_ERR_INVALID, with nothing launched, for a NULL operand, a blank outside [0, alphabet_size), a sample_stride other than 0 or
+ * num_candidates, a short workspace, minibatch > 65535, or a shape ocr_ctc_align_supported refuses (the ranges of ocr_ctc_score_supported). */
+int ocr_ctc_align_supported(int alphabet_size, int max_time, int max_label_len, int num_candidates);
+int ocr_ctc_align_workspace_size(int alphabet_size, int max_time, int minibatch, int num_candidates, int max_label_len, size_t* bytes);
+int ocr_ctc_align(const float* activations, const int* input_lengths, const int* cand_labels, const int* cand_lengths, int sample_stride,
+                  int alphabet_size, int minibatch, int max_time, int num_candidates, int max_label_len, int blank_label,
+                  int* start, int* end, float* score, float* path_cost, void* workspace, size_t workspace_bytes, void* stream);
 /* best-path decode (argmax, collapse repeats, drop blank): the greedy counterpart of
  * tf.nn.ctc_beam_search_decoder + sparse_tensor_to_dense(default 0) at network.py:656-657 / test.py:30-31.
  * decoded: int32 [minibatch, max_time] padded with pad_value; decoded_lengths: int32 [minibatch]. */

@@ -1003,6 +1003,73 @@ class Engine(object):
         return [[([int(v) for v in lexicon[int(index[n, j])] if v != 0], float(log_post[n, j])) for j in range(int(count[n]))]
                 for n in range(index.shape[0])]
 
+    @staticmethod
+    def _spans_of(strings, start, end, score, path_cost):
+        """Per sample the list of (label, start_frame, end_frame, confidence) of its string from ops.ctc_align's results (host arrays);
+        confidence = exp(score / frames), the geometric mean of the character's probability over its frames.  [] where path_cost is +inf."""
+        out = []
+        for n, s in enumerate(strings):
+            if not np.isfinite(path_cost[n]):
+                out.append([])
+                continue
+            out.append([(int(c), int(start[n, j]), int(end[n, j]), float(np.exp(np.float64(score[n, j]) / (int(end[n, j]) - int(start[n, j]) + 1))))
+                        for j, c in enumerate(s)])
+        return out
+
+    def _align_strings(self, logits, seq_len, strings, blank):
+        """ops.ctc_align of one string per sample (label lists; None = nothing to align: no spans, path_cost +inf) on logits that are on the
+        device already -> (spans, path_cost as numpy)."""
+        lens = np.array([-1 if s is None else len(s) for s in strings], np.int32)
+        if lens.max() > self.SCORE_MAX_LABEL_LEN:
+            raise ValueError('label of %d characters (at most %d)' % (lens.max(), self.SCORE_MAX_LABEL_LEN))
+        dense = np.zeros((len(strings), max(int(lens.max()), 1)), np.int32)
+        for n, s in enumerate(strings):
+            if s:
+                dense[n, :len(s)] = s
+        labels, lengths = torch.from_numpy(dense).to(self.device), torch.from_numpy(lens).to(self.device)
+        start, end, score, cost = (v.cpu().numpy() for v in ops.ctc_align(logits, seq_len, labels, lengths, blank=blank))
+        return self._spans_of([s or [] for s in strings], start, end, score, cost), cost
+
+    def align(self, data, seq_len, labels, blank=0):
+        """Where each character sits: the best (Viterbi) alignment of sample n's transcript labels[n] (a list of N label lists, blank `blank`)
+        against its logits, from one forward pass.  -> (spans, path_cost): spans[n] = [(label, start_frame, end_frame, confidence), ...] with
+        frames inclusive and confidence = exp(score / frames) in (0, 1], [] for a sample that cannot emit its label; path_cost [N] float32 numpy,
+        minus the log-probability of the best path, +inf for such a sample."""
+        if len(labels) != data.shape[0]:
+            raise ValueError('%d label lists for %d samples' % (len(labels), data.shape[0]))
+        strings = [[int(v) for v in l] for l in labels]
+        logits = self.forward(data, seq_len)
+        return self._align_strings(logits, self.plan(data.shape[0], data.shape[1]).seq_len, strings, blank)
+
+    def decode_spans(self, data, seq_len, method='greedy', lexicon=None):
+        """decode and align from the same forward pass (the logits stay on the device between the two): -> (strings as decode(method=...) returns
+        them, spans as align returns them for those strings).  method 'greedy' or 'lexicon', both with blank 0; the beam decoder's blank is C - 1
+        and its results are not aligned here."""
+        if method not in ('greedy', 'lexicon'):
+            raise ValueError("decode_spans takes method 'greedy' or 'lexicon' (got %r)" % (method,))
+        if method == 'lexicon' and lexicon is None:
+            raise ValueError("decode_spans(method='lexicon') needs a lexicon")
+        logits = self.forward(data, seq_len)
+        sp_len = self.plan(data.shape[0], data.shape[1]).seq_len
+        if method == 'greedy':
+            # the decoded labels [N, T] and their lengths go from the decoder to the aligner as they are; a string beyond 255 characters has no spans
+            out, lens = ops.ctc_greedy_decode(logits, sp_len, blank=0, pad_value=0)
+            width = max(min(int(out.shape[1]), self.SCORE_MAX_LABEL_LEN), 1)
+            start, end, score, cost = (v.cpu().numpy() for v in ops.ctc_align(logits, sp_len, out[:, :width].contiguous(), lens, blank=0))
+            out, lens = out.cpu().numpy(), lens.cpu().numpy()
+            strings = [[int(v) for v in out[i, :lens[i]] if v != 0] for i in range(out.shape[0])]
+            return strings, self._spans_of(strings, start, end, score, cost)
+        if isinstance(lexicon, LexiconTrie):
+            if lexicon.blank != 0:
+                raise ValueError('blank 0, but the LexiconTrie was built with blank %d' % lexicon.blank)
+            best = ops.ctc_score_trie(logits, sp_len, lexicon)[1].cpu().numpy()
+        else:
+            labels, lengths = self._pack_lexicon(lexicon)
+            best = ops.ctc_score(logits, sp_len, labels, lengths, blank=0)[1].cpu().numpy()
+        picked = [[int(v) for v in lexicon[b]] if b >= 0 else None for b in best]
+        spans = self._align_strings(logits, sp_len, picked, 0)[0]
+        return [[v for v in s if v != 0] if s is not None else [] for s in picked], spans
+
     def setup_optimizer(self, solver=None, lr=None):
         c = self.cfg.TRAIN
         self.solver = ops.SOLVERS.get(solver or c.SOLVER, 1)       # reference: anything else -> Momentum (train.py:76)

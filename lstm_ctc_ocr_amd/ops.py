@@ -241,6 +241,49 @@ def ctc_topk(costs, k, log_norm=None, workspace=None):
     return index, cost, log_post, count
 
 
+def ctc_align_supported(C, T, max_label_len, K):
+    """C <= 16384 classes, strings of up to 255 characters, up to 65536 of them per sample, any T (host arithmetic only)."""
+    return bool(nat.lib().ocr_ctc_align_supported(C, T, max_label_len, K))
+
+
+def ctc_align_workspace_bytes(C, max_time, minibatch, K, max_label_len):
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_align_workspace_size", C, max_time, minibatch, K, max_label_len, ctypes.byref(sz))
+    return sz.value
+
+
+def ctc_align(acts, input_lengths, labels, label_lengths, blank=0, shared=False, workspace=None):
+    """The best (Viterbi) alignment of strings against the logits acts f32 [T, N, C] (unnormalised).  labels int32 [N, L] with lengths [N]: one
+    transcript per sample; [N, K, L] with lengths [N, K]: K strings per sample; with shared=True [K, L] with lengths [K]: K strings for every
+    sample.  -> (start, end: int32 [N, K, L], the first and last frame of each character; score f32 [N, K, L], the character's log-probability
+    summed over its frames; path_cost f32 [N, K], minus the log-probability of the best path), the K axis squeezed for the [N, L] form.
+    -1 / -1 / -inf beyond a string's length and for a string the sample cannot emit, whose path_cost is +inf."""
+    T, N, C = acts.shape
+    own = not shared and labels.dim() == 2
+    want = 2 if (shared or own) else 3
+    if labels.dim() != want or label_lengths.dim() != want - 1 or tuple(labels.shape[:-1]) != tuple(label_lengths.shape) or \
+            (not shared and labels.shape[0] != N):
+        raise ValueError('labels %s / lengths %s do not fit %s for %d samples'
+                         % (tuple(labels.shape), tuple(label_lengths.shape), 'a shared [K, L] list' if shared else 'the [N, L] or [N, K, L] layout', N))
+    _dev(acts)
+    K = 1 if own else int(labels.shape[-2])
+    Lmax = int(labels.shape[-1])
+    if workspace is None:
+        workspace = torch.empty(ctc_align_workspace_bytes(C, T, N, K, Lmax), dtype=torch.uint8, device=acts.device)
+    start = torch.empty((N, K, Lmax), dtype=torch.int32, device=acts.device)
+    end = torch.empty((N, K, Lmax), dtype=torch.int32, device=acts.device)
+    score = torch.empty((N, K, Lmax), dtype=F32, device=acts.device)
+    path_cost = torch.empty((N, K), dtype=F32, device=acts.device)
+    # (strings of no characters only: Lmax = 0 and no storage; any non-NULL address does, no word of it is read or written)
+    some = labels.numel() > 0
+    call("ocr_ctc_align", ptr(acts), ptr(input_lengths), ptr(labels) if some else ptr(label_lengths), ptr(label_lengths), 0 if shared else K,
+         C, N, T, K, Lmax, blank, ptr(start) if some else ptr(path_cost), ptr(end) if some else ptr(path_cost),
+         ptr(score) if some else ptr(path_cost), ptr(path_cost), ptr(workspace), workspace.numel(), _st())
+    if own:
+        return start[:, 0], end[:, 0], score[:, 0], path_cost[:, 0]
+    return start, end, score, path_cost
+
+
 def ctc_greedy_decode(acts, input_lengths, blank=0, pad_value=0):
     T, N, C = acts.shape
     out = torch.empty((N, T), dtype=torch.int32, device=acts.device)
