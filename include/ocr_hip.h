@@ -291,6 +291,15 @@ typedef struct ocr_tn_job {
 } ocr_tn_job;
 int ocr_gemm_tn_jobs_supported(const ocr_tn_job* jobs, int njobs);
 int ocr_gemm_tn_jobs_bf16(const ocr_tn_job* jobs, int njobs, void* stream);
+/* Two such jobs AND an independent plain GEMM (ocr_gemm_nt_bf16's arguments without `splits`) in ONE launch: the jobs' tiles hold one CU each
+ * (128 KiB of LDS) and leave the other CUs idle; the GEMM's 256 x 128-tile workgroups run there.  Computes what ocr_gemm_tn_jobs_bf16(jobs, 2)
+ * and ocr_gemm_nt_bf16(...) compute, bit for bit; neither part may read what the other writes.  ocr_gemm_tn_jobs_nt_supported (host-only,
+ * nothing launched) is the policy: two covered jobs whose tiles leave at least a quarter of the CUs free, a GEMM with K % 64 == 0, N % 4 == 0,
+ * N >= 128, M >= 1024 and no accumulate flag.  OCR_STATUS_INVALID otherwise: nothing was launched, issue the two launches. */
+int ocr_gemm_tn_jobs_nt_supported(const ocr_tn_job* jobs, int njobs, int M, int N, int K, int flags);
+int ocr_gemm_tn_jobs_nt_bf16(const ocr_tn_job* jobs, int njobs, const void* P, long ldp, const void* Q, long ldq, void* out, long ldo,
+                             int M, int N, int K, const float* bias, const void* mask, long ldmask, int flags, int row_group,
+                             int row_skip, int swap_inner, int swap_outer, void* stream);
 /* A/B knob: 2 (default) = nine-tap slab kernel for conv weight gradients when a workspace is given (else as 1);
  * 1 = LDS-DMA per-tap tiles + fp32 atomics where I,J % 128 == 0; 0 = register-staged kernel */
 int ocr_set_wgrad_engine(int engine);

@@ -59,6 +59,8 @@ _SIGS = {
     "ocr_gemm_tn_batched_bf16": ([_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _I, _P, _L, _P], _I),
     "ocr_gemm_tn_jobs_supported": ([_P, _I], _I),
     "ocr_gemm_tn_jobs_bf16": ([_P, _I, _P], _I),
+    "ocr_gemm_tn_jobs_nt_supported": ([_P, _I, _I, _I, _I, _I], _I),
+    "ocr_gemm_tn_jobs_nt_bf16": ([_P, _I, _P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _P], _I),
     "ocr_lstm_xh": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _P], _I),
     "ocr_set_wgrad_engine": ([_I], _I),
     "ocr_conv3x3_bf16": ([_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P], _I),
@@ -170,14 +172,14 @@ def declared_symbols(header=HEADER_PATH):
 
 
 def source_build_id(csrc=os.path.join(_HERE, "csrc"), experiments=False):
-    """The id `make` compiles into the library (csrc/Makefile: sha256 over the sorted sources, common.h, conv_plan.h, ctc_common.h and the Makefile,
+    """The id `make` compiles into the library (csrc/Makefile: sha256 over the sorted sources, common.h, conv_plan.h, ctc_common.h, igemm_body.h and the Makefile,
     16 hex digits; the experiments flavour adds the suffix '-exp'), recomputed from the source tree: equal to build_id() unless the .so
     is stale."""
     import glob
     import hashlib
     rel = [os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*.hip"))]
     h = hashlib.sha256()
-    for f in sorted(rel) + ["common.h", "conv_plan.h", "ctc_common.h", "Makefile"]:          # make's $(sort ...) orders the same byte-wise way
+    for f in sorted(rel) + ["common.h", "conv_plan.h", "ctc_common.h", "igemm_body.h", "Makefile"]:          # make's $(sort ...) orders the same byte-wise way
         h.update(open(os.path.join(csrc, f), "rb").read())
     return h.hexdigest()[:16] + ("-exp" if experiments else "")
 

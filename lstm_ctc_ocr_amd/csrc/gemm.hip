@@ -264,6 +264,7 @@ extern "C" int ocr_set_gemm_engine(int mode) {
     g_use_igemm = mode != 0; g_use_halo = mode == 1; g_ig_stages = (mode == 2) ? 2 : 3;
     return OCR_OK;
 }
+bool gemm_uses_igemm() { return g_use_igemm != 0; }   // gemm_tn3.hip's paired launch runs the large-tile engine's workgroups: only while it is on
 
 // ------------------------------------------------------------------------------------------
 // C ABI

@@ -15,6 +15,7 @@
 // source chunk and again in the read address; ds_read_b64_tr_b16 delivers 4 consecutive m of one channel per lane.
 // Requires I % 128 == 0, J % 128 == 0; other shapes stay on gemm_tn2 / gemm_tn.
 #include "common.h"
+#include "igemm_body.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -263,11 +264,43 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
+// The weight-gradient tiles AND an independent plain GEMM in ONE grid (wgrad9.hip's paired slab launch, for the plain products): blocks
+// [0, nblk_tn) are the two jobs' 128 x 128 tiles on tn3_body, as in gemm_tn3_kernel; the rest are the GEMM's 256 x 128 tiles on igemm.hip's
+// eight-wave plain-mode body.  The tiles need 128 KiB of LDS, so a CU holds one workgroup and a tile count below the CU count leaves the
+// other CUs idle for the whole launch (160 tiles of 63 stages on 256 CUs: 96 idle for 49 us); the tiles go FIRST so that all of them start
+// at once, the GEMM's workgroups start on the CUs they leave empty and follow on whichever CU frees up.  Every workgroup runs the code and
+// the tile it has in a launch of its own, on its index within its own part of the grid: the results are the same bits.  No workgroup
+// waits for another.  (Each body's XCD-aware remap places tiles by (index within its part) & 7 while the hardware deals by blockIdx & 7:
+// where nblk_tn is no multiple of 8 the GEMM's map is rotated against the XCDs — it loses L2 locality, nothing else.)
+// The GEMM body runs TWO LDS stages (96 KiB, inside the tiles' 128 KiB): measured against three (144 KiB), the step is 3 us shorter
+// (profiles/r25a_stage_ab.log: 1.0743 against 1.0774 ms, disjoint ranges) — with eight K tiles per workgroup the third stage buys no overlap.
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_tn3_nt_kernel(Tn3Job j0, Tn3Job j1, IgArgs nt, int nblk0, int nblk_tn) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int bid = (int)blockIdx.x;
+    if (bid >= nblk_tn) {
+        ig_body<128, 0, 2, 8>(nt, bid - nblk_tn, smem, (const bf16_t*)tn3_zero_page);
+        return;
+    }
+    const int kh = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+    if (bid < nblk0) {
+        if (kh == 0) tn3_body<0, 4>(j0, bid, smem); else tn3_body<1, 4>(j0, bid, smem);
+    } else {
+        if (kh == 0) tn3_body<0, 4>(j1, bid - nblk0, smem); else tn3_body<1, 4>(j1, bid - nblk0, smem);
+    }
+}
+
 static bool tn3_covers(const Tn3Job& j) {
     if (!j.A || !j.B || !j.out || j.Mk < 256 || j.I <= 0 || j.J <= 0 || (j.I & 127) || (j.J & 127) || j.nbatch < 1) return false;
     if ((j.lda & 7) || (j.ldb & 7) || (j.sA & 7) || (j.sB & 7) || ((size_t)j.A & 15) || ((size_t)j.B & 15)) return false;     // 16-byte DMA chunks
     if (j.grp < 0 || j.skip < 0 || (j.grp == 0 && j.skip != 0)) return false;
     return (long)(j.I >> 7) * (j.J >> 7) * j.nbatch <= 0x7fffffL;
+}
+static int tn3_tiles(const Tn3Job& j) { return (j.I >> 7) * (j.J >> 7) * j.nbatch; }
+// kernel-selection knob OCR_TN3_NST: 4 stages (prefetch distance 2) / 5 (distance 3, all 160 KiB of LDS)
+static int tn3_nst() {
+    static int nst = -1;
+    if (nst < 0) { const char* e = getenv("OCR_TN3_NST"); nst = (e && atoi(e) == 5) ? 5 : 4; }      // measured equal (profiles/r04d: 1.2682 / 1.2681 ms per step): 4
+    return nst;
 }
 // 1 = ocr_gemm_tn_jobs_bf16 takes these jobs (host-only query)
 extern "C" int ocr_gemm_tn_jobs_supported(const void* jobs, int njobs) {
@@ -281,10 +314,9 @@ extern "C" int ocr_gemm_tn_jobs_supported(const void* jobs, int njobs) {
 extern "C" int ocr_gemm_tn_jobs_bf16(const void* jobs, int njobs, void* stream) {
     if (!ocr_gemm_tn_jobs_supported(jobs, njobs)) return OCR_ERR_INVALID;
     const Tn3Job* j = (const Tn3Job*)jobs;
-    const int t0 = (j[0].I >> 7) * (j[0].J >> 7) * j[0].nbatch;
-    const int t1 = njobs > 1 ? (j[1].I >> 7) * (j[1].J >> 7) * j[1].nbatch : 0;
-    static int nst = -1;                             // kernel-selection knob OCR_TN3_NST: 4 stages (prefetch distance 2) / 5 (distance 3, all 160 KiB of LDS)
-    if (nst < 0) { const char* e = getenv("OCR_TN3_NST"); nst = (e && atoi(e) == 5) ? 5 : 4; }      // measured equal (profiles/r04d: 1.2682 / 1.2681 ms per step): 4
+    const int t0 = tn3_tiles(j[0]);
+    const int t1 = njobs > 1 ? tn3_tiles(j[1]) : 0;
+    const int nst = tn3_nst();
     const int lds = nst * 2 * 64 * 256;              // stages x (A tile | B tile); the K-half exchange (64 KiB) reuses them
     if (nst == 4) {
         if (ocr_allow_lds<gemm_tn3_kernel<4>>(lds) != hipSuccess) return OCR_ERR_EXEC;
@@ -293,6 +325,54 @@ extern "C" int ocr_gemm_tn_jobs_bf16(const void* jobs, int njobs, void* stream) 
         if (ocr_allow_lds<gemm_tn3_kernel<5>>(lds) != hipSuccess) return OCR_ERR_EXEC;
         gemm_tn3_kernel<5><<<t0 + t1, 512, lds, (hipStream_t)stream>>>(j[0], njobs > 1 ? j[1] : j[0], t0);
     }
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}
+
+// ---- the weight-gradient jobs and an independent plain GEMM in one launch ----------------------------------------------------------
+bool gemm_uses_igemm();                              // gemm.hip: the large-tile engine is on (ocr_set_gemm_engine)
+// THE pairing policy, stated once (ocr_gemm_tn_jobs_nt_supported and the launch both ask here).  A pair is taken when
+//   * there are two covered jobs, on the four-stage tile body (the only one the paired kernel instantiates);
+//   * the GEMM is one the large-tile engine takes in plain mode on its 512-thread, 256 x 128-tile instance: K % 64 == 0, N % 4 == 0, N >= 128,
+//     M >= 1024, an epilogue without accumulation or atomics;
+//   * the tiles leave at least a QUARTER of the CUs free.  The GEMM's workgroups have only the free CUs until the first tile ends, so on a
+//     fraction f of the chip the GEMM takes 1 / f of its own launch's time, and the pair is shorter than the two launches only while that is
+//     less than both together: 1 / f < 1 + t_tiles / t_gemm.  At the headline's ratio (49.3 : 17.6 us) that is f > 0.26; the policy sees shapes,
+//     not times, and both launches scale with the same row count, so the bound is that ratio's: a quarter.  (256 CUs: at most 192 tiles.)
+static bool tn3_nt_pair_ok(const Tn3Job* j, int njobs, int M, int N, int K, int flags) {
+    if (!j || njobs != 2 || !tn3_covers(j[0]) || !tn3_covers(j[1]) || tn3_nst() != 4) return false;
+    if (!gemm_uses_igemm() || !ig_covers(M, N, K, flags, 0, 0) || N < 128) return false;
+    const long tiles = (long)tn3_tiles(j[0]) + tn3_tiles(j[1]);
+    const int cus = ocr_cu_count();
+    return tiles < cus && 4 * (cus - tiles) >= cus;
+}
+// 1 = ocr_gemm_tn_jobs_nt_bf16 takes these two jobs with an M x N x K GEMM of these epilogue flags (host-only query, nothing launched)
+extern "C" int ocr_gemm_tn_jobs_nt_supported(const void* jobs, int njobs, int M, int N, int K, int flags) {
+    return tn3_nt_pair_ok((const Tn3Job*)jobs, njobs, M, N, K, flags) ? 1 : 0;
+}
+// jobs: HOST array of 2 ocr_tn_job, as for ocr_gemm_tn_jobs_bf16; the other arguments are ocr_gemm_nt_bf16's without `splits`.  ONE launch
+// computes what ocr_gemm_tn_jobs_bf16(jobs, 2) and ocr_gemm_nt_bf16(...) compute, bit for bit; neither part may read what the other writes.
+// OCR_STATUS_INVALID where ocr_gemm_tn_jobs_nt_supported says no: nothing was launched, the caller issues the two launches.
+extern "C" int ocr_gemm_tn_jobs_nt_bf16(const void* jobs, int njobs, const void* P, long ldp, const void* Q, long ldq, void* out, long ldo,
+                                        int M, int N, int K, const float* bias, const void* mask, long ldmask, int flags, int row_group,
+                                        int row_skip, int swap_inner, int swap_outer, void* stream) {
+    const Tn3Job* j = (const Tn3Job*)jobs;
+    if (!P || !Q || !out || !tn3_nt_pair_ok(j, njobs, M, N, K, flags)) return OCR_ERR_INVALID;
+    if (((flags & IG_BIAS) && !bias) || ((flags & IG_MASK) && !mask)) return OCR_ERR_INVALID;
+    if ((flags & IG_ROWSWAP) && (swap_inner <= 0 || swap_outer <= 0)) return OCR_ERR_INVALID;
+    if (row_group < 0 || row_skip < 0) return OCR_ERR_INVALID;
+    IgArgs g = {};
+    g.P = (const bf16_t*)P; g.Q = (const bf16_t*)Q; g.ldp = ldp; g.ldq = ldq; g.M = M; g.N = N; g.K = K;
+    g.grp = row_group; g.skip = row_skip; g.out = out; g.ldo = ldo; g.bias = bias;
+    g.mask = (const bf16_t*)mask; g.ldmask = ldmask; g.flags = flags; g.swap_inner = swap_inner; g.swap_outer = swap_outer;
+    // the job with the longer contraction in front (its tiles are the launch's critical path); equal ones keep the caller's order
+    const int first = j[1].Mk > j[0].Mk ? 1 : 0;
+    const int t0 = tn3_tiles(j[first]), t1 = tn3_tiles(j[first ^ 1]);
+    const int nblk_nt = ((M + 255) / 256) * ((N + 127) / 128);
+    constexpr int TN_LDS = 4 * 2 * 64 * 256, NT_LDS = ig_lds_bytes<128, 2, 8>();
+    constexpr int LDS = NT_LDS > TN_LDS ? NT_LDS : TN_LDS;       // the larger of the two bodies' needs
+    if (ocr_allow_lds<gemm_tn3_nt_kernel>(LDS) != hipSuccess) return OCR_ERR_EXEC;
+    gemm_tn3_nt_kernel<<<t0 + t1 + nblk_nt, 512, LDS, (hipStream_t)stream>>>(j[first], j[first ^ 1], g, t0, t0 + t1);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }

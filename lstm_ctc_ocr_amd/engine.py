@@ -40,6 +40,7 @@ ALIGN = 64               # parameter offsets are multiples of 64 elements (256 B
 #     OCR_W9_PAIR [1]            0: every 3x3 weight-gradient slab kernel is a launch of its own, none waits to share a launch with the next layer's
 #     OCR_TN_JOBS [1]            0: every plain weight-gradient product is a launch of its own, no paired gemm_tn3 launch
 #     OCR_TN_SIDE [0]            1: the paired launch runs on a side stream beside the main chain
+#     OCR_TN_NT_PAIR [1]         0: conv5's data-gradient GEMM stays a launch of its own behind the paired gemm_tn3 launch, not inside it
 #     OCR_OVERLAP_ALLREDUCE [1]  0: data parallel without the split schedule: one all-reduce after the whole backward pass
 #     OCR_DP_GRAPH [0]           '1': the whole data-parallel step as ONE graph with captured collectives (opt-in)
 #     OCR_FORCE_ALLREDUCE [unset] any value: the RCCL call is exercised on a 1-rank group (tests)
@@ -167,6 +168,9 @@ class Engine(object):
         self.w9_flush_bytes = int(_number('OCR_W9_FLUSH_MB', 80, float) * (1 << 20))    # slab bytes after which the pending reductions run (0: one at the end of the body); 80 MB: profiles/r04e
         self.tn_defer = _switch('OCR_TN_JOBS')              # pairs of plain weight-gradient products as one gemm_tn3 launch
         self.tn_side = _switch('OCR_TN_SIDE', False)             # ... on a side stream beside the main chain's short kernels
+        # OCR_TN_NT_PAIR=0: the GEMM issued right behind the paired launch (conv5's data gradient) stays a launch of its own (default: it runs
+        # inside that launch on the CUs the tiles leave idle where ocr_gemm_tn_jobs_nt_supported accepts — same bits, one launch less)
+        self.tn_nt_pair = _switch('OCR_TN_NT_PAIR')
         self.side_stream = torch.cuda.Stream(device=self.device) if (self.tn_side and torch.device(self.device).type == 'cuda') else None
         self.group = group
         self.world = 1
@@ -663,21 +667,28 @@ class Engine(object):
         self._release_w9(sp)
         self._flush_w9(sp)
 
-    def tn_push(self, sp, job, keep, fallback):
+    def tn_push(self, sp, job, keep, fallback, nt=None):
         """A plain weight-gradient product (X^T dY of conv5 / of the BiLSTM cells) joins the pending list; TWO of them go out as ONE launch of
         the ping-pong kernel (csrc/gemm_tn3.hip: no split over the contraction, no atomics).  `keep`: tensors the descriptor points into;
         `fallback`: the product as its own launch (gemm_tn2), used when it stays alone — with a split over the pixels that kernel fills the
-        chip better than 64-96 unsplit tiles would."""
+        chip better than 64-96 unsplit tiles would.  `nt`: (P, Q, out, M, N, K) of a plain GEMM the caller would issue right behind this
+        call, independent of every pending product; returns True when that GEMM went out INSIDE the paired launch (the caller skips it)."""
         if not self.tn_defer or not ops.gemm_tn_jobs_supported([job]):
             fallback()
-            return
+            return False
         sp.tn_pending.append((job, keep, fallback))
         if len(sp.tn_pending) == 2:
-            self._flush_tn(sp)
+            return self._flush_tn(sp, nt)
+        return False
 
-    def _flush_tn(self, sp):
+    def _flush_tn(self, sp, nt=None):
         pend, sp.tn_pending = sp.tn_pending, []
         if len(pend) == 2:
+            jobs = [pend[0][0], pend[1][0]]
+            if nt is not None and self.tn_nt_pair and not self.tn_side and ops.gemm_tn_jobs_nt_supported(jobs, nt[3], nt[4], nt[5]):
+                # the tiles of the two products hold 160 of 256 CUs for the whole launch; the GEMM's workgroups take the other 96
+                ops.gemm_tn_jobs_nt(jobs, nt[0], nt[1], nt[2], M=nt[3], N=nt[4], K=nt[5])
+                return True
             if self.tn_side:
                 # the two plain weight-gradient products (47 us, operand-fill-bound on 160 of 256 CUs) are needed by the optimiser / the
                 # exchange only: they run on a side stream beside the short kernels that follow on the main chain (conv5's data gradient,
@@ -692,6 +703,7 @@ class Engine(object):
         else:
             for _, _, fallback in pend:
                 fallback()
+        return False
 
     def _join_tn(self, sp):
         if sp.tn_side_open:

@@ -520,17 +520,23 @@ class _ConvFullOp(_ConvOp):
         Wo, M, K = o[1], o[0] * o[1] * o[2], self.kh * H * C
         pdy, finish = e.grad_dst(sp, self.prev)
         dz2, dw2 = dz.view(M, self.co), dw.view(K, self.co)
-        e.tn_push(sp, ops.tn_job(x, H * C, dz2, self.co, dw2, self.co, M, K, self.co, row_group=Wo, row_skip=self.kh - 1, colsum=db),
-                  (x, dz2, dw2, db),
-                  lambda: ops.gemm_tn(x, dz2, dw2, Mk=M, I=K, J=self.co, lda=H * C, ldb=self.co,
-                                      ldo=self.co, row_group=Wo, row_skip=self.kh - 1, colsum=db))
-        if pdy is not None:
-            if self.prev.mask_in_consumer or self.kh != 2:
-                raise NotImplementedError('%s: data gradient of a full-height VALID conv is lowered for k_h = 2 '
-                                          'behind a non-ReLU producer' % self.name)
+        # the data gradient's GEMM dz W -> column matrix reads dz and the weights' bf16 shadow only: where the library's policy accepts it runs
+        # INSIDE the launch this product completes (Engine.tn_push), on the CUs the weight-gradient tiles leave idle
+        nt = None
+        if pdy is not None and not self.prev.mask_in_consumer and self.kh == 2:
             col = sp.buf[self.key + '/col']
             wsh = e.shadow(self.name + '/weights').view(K, self.co)      # [K][co] bf16, k = co contiguous
-            ops.gemm_nt(dz2, wsh, out=col, M=M, N=K, K=self.co)
+            nt = (dz2, wsh, col, M, K, self.co)
+        paired = e.tn_push(sp, ops.tn_job(x, H * C, dz2, self.co, dw2, self.co, M, K, self.co, row_group=Wo, row_skip=self.kh - 1, colsum=db),
+                           (x, dz2, dw2, db),
+                           lambda: ops.gemm_tn(x, dz2, dw2, Mk=M, I=K, J=self.co, lda=H * C, ldb=self.co,
+                                               ldo=self.co, row_group=Wo, row_skip=self.kh - 1, colsum=db), nt=nt)
+        if pdy is not None:
+            if nt is None:
+                raise NotImplementedError('%s: data gradient of a full-height VALID conv is lowered for k_h = 2 '
+                                          'behind a non-ReLU producer' % self.name)
+            if not paired:
+                ops.gemm_nt(dz2, wsh, out=col, M=M, N=K, K=self.co)
             bn = getattr(self.prev, 'bn_fused_into', None)
             if bn is None or bn.key not in sp.col_bn:       # else: inside that layer's batch-norm statistics pass (alloc recorded col there)
                 ops.conv5_col2im(col, pdy, N, W, H * C)

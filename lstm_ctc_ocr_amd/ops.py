@@ -492,6 +492,28 @@ def gemm_tn_jobs(jobs):
     call("ocr_gemm_tn_jobs_bf16", ctypes.cast(arr, ctypes.c_void_p), len(jobs), _st())
 
 
+def gemm_tn_jobs_nt_supported(jobs, M, N, K, flags=0):
+    """Whether gemm_tn_jobs_nt takes these two products with an M x N x K plain GEMM of these epilogue flags in one launch (host-only query:
+    the library's policy — two covered jobs whose tiles leave a quarter of the CUs free, a GEMM of the 256 x 128-tile instance)."""
+    arr = (TnJob * len(jobs))(*jobs)
+    return bool(nat.lib().ocr_gemm_tn_jobs_nt_supported(ctypes.cast(arr, ctypes.c_void_p), len(jobs), int(M), int(N), int(K), int(flags)))
+
+
+def gemm_tn_jobs_nt(jobs, P, Q, out, *, M=None, N=None, K=None, ldp=None, ldq=None, ldo=None, row_group=0, row_skip=0):
+    """gemm_tn_jobs(jobs) and gemm_nt(P, Q, out, ...) in ONE launch, bit for bit: the GEMM's workgroups run on the CUs the products' tiles
+    leave idle.  Neither part may read what the other writes.  Only where gemm_tn_jobs_nt_supported says so."""
+    M = P.shape[0] if M is None else M
+    K = P.shape[1] if K is None else K
+    N = Q.shape[0] if N is None else N
+    ldp = P.stride(0) if ldp is None else ldp
+    ldq = Q.stride(0) if ldq is None else ldq
+    ldo = out.stride(0) if ldo is None else ldo
+    arr = (TnJob * len(jobs))(*jobs)
+    call("ocr_gemm_tn_jobs_nt_bf16", ctypes.cast(arr, ctypes.c_void_p), len(jobs), ptr(_dev(P)), ldp, ptr(Q), ldq, ptr(out), ldo, M, N, K,
+         None, None, 0, EPI_OUT_F32 if out.dtype == F32 else 0, row_group, row_skip, 0, 0, _st())
+    return out
+
+
 def lstm_xh(x2d, hout, seq_len, xh, Nb, T, D, U, ndir=2):
     call("ocr_lstm_xh", ptr(_dev(x2d)), ptr(hout), ptr(seq_len), ptr(xh), Nb, T, D, U, ndir, _st())
     return xh

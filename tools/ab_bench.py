@@ -6,7 +6,11 @@ times, so drift of the box shows up as spread inside every variant instead of as
   python tools/ab_bench.py --tag r03a base: mfma32:OCR_HALO_MFMA32=1 "old:OCR_W9_DEFER=0,OCR_FUSE_PACK_BIAS=0"
   python tools/ab_bench.py --tag r03deep --bench-args "--workload deep" base: nodefer:OCR_W9_DEFER=0
 
-Each spec is label:ENV=VALUE[,ENV=VALUE...] (an empty list = the defaults).  Prints one line per variant (mean / min / max ms per step,
+  python tools/ab_bench.py --tag r25 --rounds 3 parent@/path/to/parent_checkout: this:
+
+Each spec is label[@DIR]:ENV=VALUE[,ENV=VALUE...] (an empty list = the defaults).  label@DIR runs DIR/bench.py — another checkout of this
+repository with its own built library, e.g. the parent commit — so two COMMITS alternate inside one call like two settings of a knob.  A run
+that times out or dies on a signal ends the whole A/B: nothing more is started on that GPU.  Prints one line per variant (mean / min / max ms per step,
 images/s of the mean, the convolution roofline number) and writes gpurun_out/<tag>_ab.json.
 """
 import argparse
@@ -18,14 +22,20 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_once(env_add, bench_args, steps, timeout):
+class Died(Exception):
+    pass
+
+
+def run_once(env_add, bench_args, steps, timeout, root=ROOT):
     env = dict(os.environ)
     env.update(env_add)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--steps', str(steps)] + bench_args
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--full', '--no-cpu-baseline', '--steps', str(steps)] + bench_args
     try:
-        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout, cwd=root)
     except subprocess.TimeoutExpired:
-        return None
+        raise Died('timed out after %d s' % timeout)
+    if out.returncode < 0 or out.returncode in (124, 134, 137, 139):
+        raise Died('exit status %d\n%s' % (out.returncode, out.stderr[-2000:]))
     for line in reversed(out.stdout.strip().splitlines()):
         if line.startswith('{'):
             try:
@@ -47,17 +57,22 @@ def main():
     variants = []
     for spec in args.specs:
         label, _, envs = spec.partition(':')
+        label, _, root = label.partition('@')
         env = dict(kv.split('=', 1) for kv in envs.split(',') if kv)
-        variants.append((label, env))
+        variants.append((label, env, os.path.abspath(root) if root else ROOT))
     bench_args = args.bench_args.split()
-    results = {label: [] for label, _ in variants}
-    for _ in range(args.rounds):
-        for label, env in variants:
-            d = run_once(env, bench_args, args.steps, args.timeout)
-            results[label].append(None if d is None else dict(ms_per_step=d['ms_per_step'], images_per_s=d['value'],
-                                                              conv_tflops=d.get('roofline', {}).get('achieved')))
+    results = {label: [] for label, _, _ in variants}
+    try:
+        for _ in range(args.rounds):
+            for label, env, root in variants:
+                d = run_once(env, bench_args, args.steps, args.timeout, root)
+                results[label].append(None if d is None else dict(ms_per_step=d['ms_per_step'], images_per_s=d['value'],
+                                                                  conv_tflops=d.get('roofline', {}).get('achieved')))
+    except Died as e:
+        print('%s: %s — no further run started' % (label, e))
+        sys.exit(1)
     table = []
-    for label, env in variants:
+    for label, env, _ in variants:
         ok = [r for r in results[label] if r]
         if not ok:
             print('%-16s no result' % label)
