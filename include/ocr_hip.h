@@ -195,6 +195,21 @@ int ocr_ctc_beam_workspace_size(int alphabet_size, int minibatch, int max_time, 
 int ocr_ctc_beam_decode(const float* activations, const int* input_lengths, int alphabet_size, int minibatch,
                         int max_time, int beam_width, int merge_repeated, int pad_value, int* decoded,
                         int* decoded_lengths, float* neg_log_prob, void* workspace, size_t workspace_bytes, void* stream);
+/* The same search with TF's top_paths and any blank class: the top_paths best prefixes of the final beam per sample, best first under the
+ * total order (log-probability descending, then the lower beam slot); entries of probability zero are never returned.
+ *   decoded: int32 [minibatch, top_paths, max_time] padded with pad_value; decoded_lengths: int32 [minibatch, top_paths];
+ *   neg_log_prob: f32 [minibatch, top_paths]; count: int32 [minibatch], the number of paths returned (the beam may hold fewer than
+ *   top_paths prefixes: C - 1 < top_paths, or few frames).  Slots at and beyond count[n] hold pad_value / length -1 / +inf: -1 is what
+ *   ocr_ctc_score and ocr_ctc_align read as "no string", 0 is the empty string.
+ * 1 <= top_paths <= beam_width <= 128 and 0 <= blank < alphabet_size; none of the operands may be NULL.  Workspace, kernel choice and
+ * ocr_set_beam_engine as for ocr_ctc_beam_decode; anything else is OCR_STATUS_INVALID and nothing is launched.
+ * blank = 0 with merge_repeated = 0 is the textbook CTC prefix search: its prefixes are label strings and neg_log_prob is comparable
+ * with ocr_ctc_score(blank_label = 0), which it never undercuts (the beam sums a subset of the string's alignments).
+ * blank = alphabet_size - 1, top_paths = 1 returns ocr_ctc_beam_decode's outputs bit for bit. */
+int ocr_ctc_beam_decode_nbest(const float* activations, const int* input_lengths, int alphabet_size, int minibatch,
+                              int max_time, int beam_width, int top_paths, int blank, int merge_repeated, int pad_value,
+                              int* decoded, int* decoded_lengths, float* neg_log_prob, int* count, void* workspace,
+                              size_t workspace_bytes, void* stream);
 /* Which kernel ocr_ctc_beam_decode runs for a shape - a host-only query like ocr_conv3x3_kernel_choice (nothing is launched, works
  * without a GPU): 0 refused, 1 table kernel, 2 wide kernel.  It honours ocr_set_beam_engine. */
 int ocr_ctc_beam_kernel_choice(int alphabet_size, int beam_width);

@@ -54,9 +54,16 @@ struct BeamArgs {
     const float* act; const int* input_len; int T, N, C, K, merge_repeated, pad_value;
     int* out; int* out_len; float* neg_log_prob;
     int* node_parent; short* node_label; int* node_slot;     // per sample: T*K + 2 entries
+    int blank, top_paths; int* count;                        // n-best entry only (NBEST = true)
 };
 
-template <bool WIDE>
+// NBEST = true is ocr_ctc_beam_decode_nbest: the caller's blank is any class and the `top_paths` best leaves are emitted.  Inside the
+// kernel the blank stays the LAST class: the log-softmax row is stored through the monotone re-indexing  k -> k (k < blank),
+// C - 1 (k == blank), k - 1 (k > blank), and a label is translated back where a path is emitted.  The re-indexing keeps the order of the
+// non-blank classes, so every "lowest class index" / "lowest candidate index" tie rule picks the class it would pick in the caller's
+// numbering, and for blank == C - 1 it is the identity.  NBEST = false is ocr_ctc_beam_decode as it always was (no re-indexing in its
+// instances, thread 0 emits the best leaf).
+template <bool WIDE, bool NBEST>
 __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -115,7 +122,13 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             __syncthreads();
             float lse = m + logf(((float*)s_cnt)[0] + ((float*)s_cnt)[1] + ((float*)s_cnt)[2] + ((float*)s_cnt)[3]);
             __syncthreads();
-            for (int k = tid; k < C; k += 256) lp[k] = row[k] - lse;
+            if constexpr (NBEST) {
+                const int ub = a.blank;                    // the caller's blank; internal index of class k (see the kernel's header)
+                // (one loop: a loop per range, below and above the blank, exposes a second global-load latency per frame and measured slower)
+                for (int k = tid; k < C; k += 256) lp[k < ub ? k : (k == ub ? C - 1 : k - 1)] = row[k] - lse;
+            } else {
+                for (int k = tid; k < C; k += 256) lp[k] = row[k] - lse;
+            }
         }
         __syncthreads();
         // (a') wide kernel: S = the M non-blank classes with the largest lp, ascending.  M-th largest key by the bisection of step (d),
@@ -323,6 +336,42 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         gen = g2;
         (void)upd_pb;
     }
+    if constexpr (NBEST) {
+        // ---- the top_paths best leaves under the total order (total descending, then lower slot), ranked by counting: thread s counts the
+        // entries ahead of it.  -inf totals are never returned (they rank behind every finite one, so they do not disturb the counts).
+        const int nb = s_misc[0], P = a.top_paths, ub = a.blank;
+        const float* tot = b_tot + gen * BEAM_MAX; const int* node = b_node + gen * BEAM_MAX;
+        int valid = 0;
+        for (int s = 0; s < nb; ++s) valid += (tot[s] != NEGINF);
+        const int cnt = min(valid, P);
+        if (tid < nb && tot[tid] != NEGINF) {
+            const float mine = tot[tid];
+            int rank = 0;
+            for (int s = 0; s < nb; ++s) rank += (tot[s] > mine || (tot[s] == mine && s < tid));
+            if (rank < P) {                                  // this thread walks its own path root-ward
+                int* o = a.out + ((size_t)n * P + rank) * a.T;
+                int len = 0;
+                for (int id = node[tid]; id > 0; id = npar[id]) { const int c = nlab[id]; o[len++] = (c < ub) ? c : c + 1; }      // reversed
+                for (int i = 0; i < len / 2; ++i) { int tmp = o[i]; o[i] = o[len - 1 - i]; o[len - 1 - i] = tmp; }
+                if (a.merge_repeated) {
+                    int w = 0;
+                    for (int i = 0; i < len; ++i) if (i == 0 || o[i] != o[i - 1]) o[w++] = o[i];
+                    len = w;
+                }
+                for (int i = len; i < a.T; ++i) o[i] = a.pad_value;
+                a.out_len[(size_t)n * P + rank] = len;
+                a.neg_log_prob[(size_t)n * P + rank] = -mine;
+            }
+        }
+        if (tid >= cnt && tid < P) {                         // no path for these slots (P <= 128 < 256 threads)
+            int* o = a.out + ((size_t)n * P + tid) * a.T;
+            for (int i = 0; i < a.T; ++i) o[i] = a.pad_value;
+            a.out_len[(size_t)n * P + tid] = -1;
+            a.neg_log_prob[(size_t)n * P + tid] = INFINITY;
+        }
+        if (tid == 0) a.count[n] = cnt;
+        return;
+    }
     // ---- best leaf, label sequence (root-ward walk), merge_repeated, output
     if (tid == 0) {
         const int nb = s_misc[0];
@@ -381,6 +430,27 @@ extern "C" int ocr_ctc_beam_workspace_size(int alphabet_size, int minibatch, int
     return OCR_OK;
 }
 
+template <bool NBEST>
+static int beam_launch(const BeamArgs& a, hipStream_t stream) {
+    if (ocr_ctc_beam_kernel_choice(a.C, a.K) == 2) {
+        const size_t lds = beam_wide_lds_bytes(a.C, a.K);
+        if (ocr_allow_lds<ctc_beam_kernel<true, NBEST>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
+        ctc_beam_kernel<true, NBEST><<<a.N, 256, lds, stream>>>(a);
+    } else {
+        const size_t lds = beam_lds_bytes(a.C, a.K);
+        if (ocr_allow_lds<ctc_beam_kernel<false, NBEST>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
+        ctc_beam_kernel<false, NBEST><<<a.N, 256, lds, stream>>>(a);
+    }
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}
+static void beam_workspace(BeamArgs& a, void* workspace) {
+    const size_t pool = (size_t)a.T * a.K + 2;
+    a.node_parent = (int*)workspace;
+    a.node_slot = a.node_parent + (size_t)a.N * pool;
+    a.node_label = (short*)(a.node_slot + (size_t)a.N * pool);
+}
+
 extern "C" int ocr_ctc_beam_decode(const float* activations, const int* input_lengths, int alphabet_size, int minibatch,
                                    int max_time, int beam_width, int merge_repeated, int pad_value, int* decoded,
                                    int* decoded_lengths, float* neg_log_prob, void* workspace, size_t workspace_bytes,
@@ -390,21 +460,26 @@ extern "C" int ocr_ctc_beam_decode(const float* activations, const int* input_le
     if (!activations || !input_lengths || !decoded || !decoded_lengths || !workspace) return OCR_ERR_INVALID;
     if (ocr_ctc_beam_workspace_size(alphabet_size, minibatch, max_time, beam_width, &need) != OCR_OK || workspace_bytes < need)
         return OCR_ERR_INVALID;
-    const size_t pool = (size_t)max_time * beam_width + 2;
     BeamArgs a = {activations, input_lengths, max_time, minibatch, alphabet_size, beam_width, merge_repeated, pad_value,
-                  decoded, decoded_lengths, neg_log_prob, nullptr, nullptr, nullptr};
-    a.node_parent = (int*)workspace;
-    a.node_slot = a.node_parent + (size_t)minibatch * pool;
-    a.node_label = (short*)(a.node_slot + (size_t)minibatch * pool);
-    if (ocr_ctc_beam_kernel_choice(alphabet_size, beam_width) == 2) {
-        const size_t lds = beam_wide_lds_bytes(alphabet_size, beam_width);
-        if (ocr_allow_lds<ctc_beam_kernel<true>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
-        ctc_beam_kernel<true><<<minibatch, 256, lds, stream>>>(a);
-    } else {
-        const size_t lds = beam_lds_bytes(alphabet_size, beam_width);
-        if (ocr_allow_lds<ctc_beam_kernel<false>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
-        ctc_beam_kernel<false><<<minibatch, 256, lds, stream>>>(a);
-    }
-    OCR_CHECK_LAUNCH();
-    return OCR_OK;
+                  decoded, decoded_lengths, neg_log_prob, nullptr, nullptr, nullptr, alphabet_size - 1, 1, nullptr};
+    beam_workspace(a, workspace);
+    return beam_launch<false>(a, stream);
+}
+
+// The top_paths best prefixes per sample, best first, for any blank class (see the kernel's header).  decoded [N, top_paths, T],
+// decoded_lengths / neg_log_prob [N, top_paths], count [N]; slots at and beyond count[n] hold pad_value / -1 / +inf.
+extern "C" int ocr_ctc_beam_decode_nbest(const float* activations, const int* input_lengths, int alphabet_size, int minibatch,
+                                         int max_time, int beam_width, int top_paths, int blank, int merge_repeated, int pad_value,
+                                         int* decoded, int* decoded_lengths, float* neg_log_prob, int* count, void* workspace,
+                                         size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    size_t need = 0;
+    if (!activations || !input_lengths || !decoded || !decoded_lengths || !neg_log_prob || !count || !workspace) return OCR_ERR_INVALID;
+    if (ocr_ctc_beam_workspace_size(alphabet_size, minibatch, max_time, beam_width, &need) != OCR_OK || workspace_bytes < need)
+        return OCR_ERR_INVALID;
+    if (top_paths < 1 || top_paths > beam_width || blank < 0 || blank >= alphabet_size) return OCR_ERR_INVALID;
+    BeamArgs a = {activations, input_lengths, max_time, minibatch, alphabet_size, beam_width, merge_repeated, pad_value,
+                  decoded, decoded_lengths, neg_log_prob, nullptr, nullptr, nullptr, blank, top_paths, count};
+    beam_workspace(a, workspace);
+    return beam_launch<true>(a, stream);
 }

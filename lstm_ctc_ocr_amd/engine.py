@@ -931,6 +931,8 @@ class Engine(object):
                           blank is class C-1; class 0 is an ordinary symbol that sparse_to_dense/ignore_value=0 strip later
                           (network.py:656-657, training.py:32).
         method='greedy' : best path with blank 0.
+        method='prefix' : the textbook CTC prefix search: the same beam search with blank 0 and merge_repeated=False.  Its prefixes are label
+                          strings (no zero occurs in them); not the reference's decoder.
         method='lexicon': the likeliest string of `lexicon` (label lists, blank 0, or a lexicon.LexiconTrie built with blank 0) under CTC; [] for a
                           sample none of them fits.  With a LexiconTrie only the arg-min leaves the device, not the N x K cost matrix."""
         if method == 'lexicon':
@@ -947,6 +949,9 @@ class Engine(object):
         logits = self.ops[-1].y(sp)
         if method == 'greedy':
             out, lens = ops.ctc_greedy_decode(logits, sp.seq_len, blank=0, pad_value=0)
+        elif method == 'prefix':
+            paths, plens, _, _ = ops.ctc_beam_nbest(logits, sp.seq_len, 1, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0)
+            out, lens = paths[:, 0], plens[:, 0]
         else:
             out, lens, _ = ops.ctc_beam_decode(logits, sp.seq_len, beam_width=beam_width, merge_repeated=True, pad_value=0)
         out = out.cpu().numpy()
@@ -1015,6 +1020,43 @@ class Engine(object):
         return [[([int(v) for v in lexicon[int(index[n, j])] if v != 0], float(log_post[n, j])) for j in range(int(count[n]))]
                 for n in range(index.shape[0])]
 
+    NBEST_MAX_K = 64            # ops.ctc_topk's limit
+
+    def decode_nbest_beam(self, data, seq_len, k=5, beam_width=100, candidates=None, rescore=True):
+        """The k likeliest strings per sample without a lexicon: the `candidates` (default k) best prefixes of the CTC prefix search (blank 0,
+        merge_repeated=False, as decode(method='prefix')), from one forward pass.  -> per sample a best-first list of at most k triples
+        (labels, log_prob, log_post).  k <= 64 and k <= candidates <= beam_width.
+        rescore=True : every candidate is scored exactly on the device (ops.ctc_score, per sample) and the k cheapest are selected there
+                       (ops.ctc_topk); log_prob = minus the exact CTC cost, in the units of score; log_post is normalised within the candidate
+                       list; the order is by exact cost.  A prefix beyond 255 labels has no exact cost and drops out.
+        rescore=False: log_prob is the beam's own score (a lower bound: the beam sums a subset of the string's alignments), log_post its
+                       normalisation over the returned paths; the order is the beam's."""
+        k, beam_width = int(k), int(beam_width)
+        candidates = k if candidates is None else int(candidates)
+        if not (1 <= k <= self.NBEST_MAX_K and k <= candidates <= beam_width):
+            raise ValueError('decode_nbest_beam takes 1 <= k <= %d and k <= candidates <= beam_width (got k = %d, candidates = %d, beam_width = %d)'
+                             % (self.NBEST_MAX_K, k, candidates, beam_width))
+        logits = self.forward(data, seq_len)
+        sp_len = self.plan(data.shape[0], data.shape[1]).seq_len
+        paths, lens, nlp, count = ops.ctc_beam_nbest(logits, sp_len, candidates, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0)
+        if rescore:
+            width = max(min(int(paths.shape[2]), self.SCORE_MAX_LABEL_LEN), 1)
+            costs, _, _, log_norm = ops.ctc_score(logits, sp_len, paths[:, :, :width].contiguous(), lens, blank=0, per_sample=True)
+            index, cost, log_post, count = (v.cpu().numpy() for v in ops.ctc_topk(costs, k, log_norm=log_norm))
+            log_prob = -cost
+        else:
+            nlp, count = nlp[:, :k].cpu().numpy(), np.minimum(count.cpu().numpy(), k)
+            log_prob = -nlp.astype(np.float64)
+            log_post = np.full(log_prob.shape, -np.inf)
+            for n in range(log_prob.shape[0]):
+                v = log_prob[n, :count[n]]
+                if v.size:
+                    log_post[n, :count[n]] = v - (v.max() + np.log(np.exp(v - v.max()).sum()))
+            index = np.tile(np.arange(k, dtype=np.int32), (log_prob.shape[0], 1))
+        paths, lens = paths.cpu().numpy(), lens.cpu().numpy()
+        return [[([int(v) for v in paths[n, index[n, j], :lens[n, index[n, j]]]], float(log_prob[n, j]), float(log_post[n, j]))
+                 for j in range(int(count[n]))] for n in range(paths.shape[0])]
+
     @staticmethod
     def _spans_of(strings, start, end, score, path_cost):
         """Per sample the list of (label, start_frame, end_frame, confidence) of its string from ops.ctc_align's results (host arrays);
@@ -1055,17 +1097,21 @@ class Engine(object):
 
     def decode_spans(self, data, seq_len, method='greedy', lexicon=None):
         """decode and align from the same forward pass (the logits stay on the device between the two): -> (strings as decode(method=...) returns
-        them, spans as align returns them for those strings).  method 'greedy' or 'lexicon', both with blank 0; the beam decoder's blank is C - 1
-        and its results are not aligned here."""
-        if method not in ('greedy', 'lexicon'):
-            raise ValueError("decode_spans takes method 'greedy' or 'lexicon' (got %r)" % (method,))
+        them, spans as align returns them for those strings).  method 'greedy', 'prefix' or 'lexicon', all with blank 0; the reference's beam
+        decoder ('beam') has blank C - 1 and its results are not aligned here."""
+        if method not in ('greedy', 'prefix', 'lexicon'):
+            raise ValueError("decode_spans takes method 'greedy', 'prefix' or 'lexicon' (got %r)" % (method,))
         if method == 'lexicon' and lexicon is None:
             raise ValueError("decode_spans(method='lexicon') needs a lexicon")
         logits = self.forward(data, seq_len)
         sp_len = self.plan(data.shape[0], data.shape[1]).seq_len
-        if method == 'greedy':
+        if method in ('greedy', 'prefix'):
             # the decoded labels [N, T] and their lengths go from the decoder to the aligner as they are; a string beyond 255 characters has no spans
-            out, lens = ops.ctc_greedy_decode(logits, sp_len, blank=0, pad_value=0)
+            if method == 'greedy':
+                out, lens = ops.ctc_greedy_decode(logits, sp_len, blank=0, pad_value=0)
+            else:
+                paths, plens, _, _ = ops.ctc_beam_nbest(logits, sp_len, 1, blank=0, merge_repeated=False, pad_value=0)
+                out, lens = paths[:, 0], plens[:, 0].contiguous()
             width = max(min(int(out.shape[1]), self.SCORE_MAX_LABEL_LEN), 1)
             start, end, score, cost = (v.cpu().numpy() for v in ops.ctc_align(logits, sp_len, out[:, :width].contiguous(), lens, blank=0))
             out, lens = out.cpu().numpy(), lens.cpu().numpy()

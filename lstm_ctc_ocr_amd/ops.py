@@ -307,6 +307,28 @@ def ctc_beam_decode(acts, input_lengths, beam_width=100, merge_repeated=True, pa
     return out, lens, nlp
 
 
+def ctc_beam_nbest(acts, input_lengths, top_paths, beam_width=100, blank=None, merge_repeated=False, pad_value=0, workspace=None):
+    """The top_paths best prefixes of the beam search, best first, with any class as the blank (None: C - 1, TF's).  blank=0 with
+    merge_repeated=False is the textbook CTC prefix search, whose costs compare with ctc_score(blank=0).
+    -> (paths [N, top_paths, T] int32, lengths [N, top_paths] int32, neg_log_prob [N, top_paths] f32, count [N] int32); slots at and beyond
+    count[n] hold pad_value / -1 / +inf."""
+    T, N, C = acts.shape
+    blank = C - 1 if blank is None else int(blank)
+    top_paths = int(top_paths)
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_beam_workspace_size", C, N, T, beam_width, ctypes.byref(sz))
+    if workspace is None or workspace.numel() < sz.value:
+        workspace = torch.empty(sz.value, dtype=torch.uint8, device=acts.device)
+    shape = (N, max(top_paths, 0))                 # (a top_paths outside the limits is the entry's to refuse)
+    paths = torch.empty(shape + (T,), dtype=torch.int32, device=acts.device)
+    lens = torch.empty(shape, dtype=torch.int32, device=acts.device)
+    nlp = torch.empty(shape, dtype=F32, device=acts.device)
+    count = torch.empty(N, dtype=torch.int32, device=acts.device)
+    call("ocr_ctc_beam_decode_nbest", ptr(_dev(acts)), ptr(input_lengths), C, N, T, beam_width, top_paths, blank, int(merge_repeated),
+         pad_value, ptr(paths), ptr(lens), ptr(nlp), ptr(count), ptr(workspace), workspace.numel(), _st())
+    return paths, lens, nlp, count
+
+
 BEAM_KERNEL_NAMES = (None, "table", "wide")
 
 
