@@ -174,6 +174,36 @@ int ocr_ctc_align_workspace_size(int alphabet_size, int max_time, int minibatch,
 int ocr_ctc_align(const float* activations, const int* input_lengths, const int* cand_labels, const int* cand_lengths, int sample_stride,
                   int alphabet_size, int minibatch, int max_time, int num_candidates, int max_label_len, int blank_label,
                   int* start, int* end, float* score, float* path_cost, void* workspace, size_t workspace_bytes, void* stream);
+/* edit_distance.hip.  Levenshtein distance (unit costs for insert, delete and substitute) between every string of a set A and every string
+ * of a set B, per sample: dist int32 [N][Ka][Kb].  String (n, i) of A starts at a + n * a_sn + i * a_ld (pitches and strides in ints) and has
+ * the raw length a_len[n * Ka + i]; a_sn == 0 is one list shared by all samples, whose lengths are a_len[i].  B alike.  One entry so covers a
+ * hypothesis against its truth (Ka = Kb = 1), the [N, K, T] paths of ocr_ctc_beam_decode_nbest against the truth or against themselves, and a
+ * shared reference list.
+ *   ignore  : a class whose occurrences are dropped from both strings before they are compared (the decoders' pad / ignore_value 0); -1 for
+ *             none.  The counted length of a string is its raw length minus the dropped characters.
+ *   "no string": a raw length below 0 (the empty slots of the n-best entry hold -1), a raw length above the pitch (a_ld / b_ld), or a counted
+ *             length above 255.  Every pair with such a string gets dist = -1, and nothing else does.  No address at or beyond a string's
+ *             start + pitch is read, whatever its length says.
+ *   a_count, b_count: int32, indexed like a_len / b_len, the counted lengths, -1 for "no string"; either may be NULL.
+ * 1 <= N <= 65535, 1 <= Ka, Kb <= 65536, N * Ka * Kb <= 2^30 (ocr_edit_distance_supported: arithmetic only).  One launch, a wave per four
+ * consecutive pairs: where all their strings have at most 15 raw characters each pair gets 16 lanes, else the pairs take the whole wave in turn
+ * (a column of the table per lane up to 63 counted characters of B, four per lane up to 255).  Integers only, fully determined: no atomics, no
+ * communication between workgroups.  OCR_ERR_INVALID, with nothing launched, for a NULL a / a_len / b / b_len / dist, a negative pitch or
+ * stride, a pointer that is not 4-byte aligned, or N, Ka, Kb out of range.
+ * ocr_edit_stats: stats[4] (int64) = {sum of dist, sum of ref_count, number with dist == 0, number counted} over those of the M pairs (dist
+ * and ref_count int32 [M]) with dist >= 0, in one launch of one workgroup: a validation batch leaves the device as four numbers.
+ * 1 <= M <= 2^30; OCR_ERR_INVALID for a NULL operand, a stats that is not 8-byte aligned or M out of range.
+ * ocr_mbr_select: minimum-Bayes-risk choice among the K candidates of every sample from their distances dist int32 [N][K][K] and costs f32
+ * [N][K] (minus log-probabilities).  Candidate j is valid when costs[n][j] is finite and dist[n][j][j] >= 0; c_min = the least valid cost,
+ * w_j = expf(c_min - c_j), Z = sum_j w_j, risk[n][i] = (sum_j w_j * dist[n][i][j]) / Z, both sums over the valid j in ascending order in
+ * fp32 with one rounding per operation (the same bits whatever the launch); +inf for an invalid i.  best[n] = the arg-min under the total
+ * order (risk, then cost, then the lower index), best_risk[n] its risk; -1 and +inf where no candidate is valid.  1 <= K <= 128, 1 <= N <= 65535;
+ * OCR_ERR_INVALID, with nothing launched, for a NULL operand or N, K out of range. */
+int ocr_edit_distance_supported(int Ka, int Kb, int N);
+int ocr_edit_distance(const int* a, const int* a_len, long a_ld, long a_sn, int Ka, const int* b, const int* b_len, long b_ld, long b_sn,
+                      int Kb, int N, int ignore, int* dist, int* a_count, int* b_count, void* stream);
+int ocr_edit_stats(const int* dist, const int* ref_count, long M, long long* stats, void* stream);
+int ocr_mbr_select(const int* dist, const float* costs, int N, int K, float* risk, int* best, float* best_risk, void* stream);
 /* best-path decode (argmax, collapse repeats, drop blank): the greedy counterpart of
  * tf.nn.ctc_beam_search_decoder + sparse_tensor_to_dense(default 0) at network.py:656-657 / test.py:30-31.
  * decoded: int32 [minibatch, max_time] padded with pad_value; decoded_lengths: int32 [minibatch]. */

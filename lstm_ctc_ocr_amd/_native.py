@@ -49,6 +49,10 @@ _SIGS = {
     "ocr_ctc_align_supported": ([_I, _I, _I, _I], _I),
     "ocr_ctc_align_workspace_size": ([_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_align": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "ocr_edit_distance_supported": ([_I, _I, _I], _I),
+    "ocr_edit_distance": ([_P, _P, _L, _L, _I, _P, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P], _I),
+    "ocr_edit_stats": ([_P, _P, _L, _P, _P], _I),
+    "ocr_mbr_select": ([_P, _P, _I, _I, _P, _P, _P, _P], _I),
     "ocr_ctc_greedy_decode":([_P, _P, _I, _I, _I, _I, _I, _P, _P, _P], _I),
     "ocr_ctc_beam_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_beam_decode": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),

@@ -1057,6 +1057,67 @@ class Engine(object):
         return [[([int(v) for v in paths[n, index[n, j], :lens[n, index[n, j]]]], float(log_prob[n, j]), float(log_post[n, j]))
                  for j in range(int(count[n]))] for n in range(paths.shape[0])]
 
+    def evaluate(self, data, seq_len, labels, method='beam', beam_width=100, per_sample=False):
+        """Character error rate and sequence accuracy of a batch from one forward pass, counted on the device: the batch is decoded as
+        decode(method=...) decodes it ('beam', 'greedy' or 'prefix'), the decoded ids stay on the device, ops.edit_distance compares each sample
+        with its own label labels[n] (a list of N label lists; class 0 dropped from both sides, as accuracy_calculation's ignore_value) and
+        ops.edit_stats sums: four integers leave the device.  -> dict: exact (samples at distance 0), edits (sum of the distances),
+        ref_chars (sum of the labels' counted lengths), counted, skipped (samples with a string beyond 255 characters: they count as wrong),
+        accuracy = exact / N (= accuracy_calculation(labels, decode(...)) when nothing is skipped), cer = edits / ref_chars (nan when
+        ref_chars is 0); with per_sample=True also distances: int32 [N] numpy, -1 for a skipped sample."""
+        if method not in ('beam', 'greedy', 'prefix'):
+            raise ValueError("evaluate takes method 'beam', 'greedy' or 'prefix' (got %r)" % (method,))
+        N = data.shape[0]
+        if len(labels) != N:
+            raise ValueError('%d label lists for %d samples' % (len(labels), N))
+        lens = np.array([len(l) for l in labels], np.int32)
+        dense = np.zeros((N, max(int(lens.max()), 1)), np.int32)
+        for n, l in enumerate(labels):
+            dense[n, :len(l)] = l
+        sp = self.plan(N, data.shape[1])
+        self._bind(sp, data, seq_len)
+        self._run(sp, 'fwd')
+        logits = self.ops[-1].y(sp)
+        if method == 'greedy':
+            out, olens = ops.ctc_greedy_decode(logits, sp.seq_len, blank=0, pad_value=0)
+        elif method == 'prefix':
+            paths, plens, _, _ = ops.ctc_beam_nbest(logits, sp.seq_len, 1, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0)
+            out, olens = paths[:, 0], plens[:, 0].contiguous()
+        else:
+            out, olens, _ = ops.ctc_beam_decode(logits, sp.seq_len, beam_width=beam_width, merge_repeated=True, pad_value=0)
+        ref, ref_len = torch.from_numpy(dense).to(self.device), torch.from_numpy(lens).to(self.device)
+        dist, _, ref_count = ops.edit_distance(out, olens, ref, ref_len, ignore=0, want_counts=True)
+        edits, ref_chars, exact, counted = (int(v) for v in ops.edit_stats(dist.view(-1), ref_count).cpu().numpy())
+        res = dict(exact=exact, edits=edits, ref_chars=ref_chars, counted=counted, skipped=N - counted, accuracy=exact * 1.0 / N,
+                   cer=edits * 1.0 / ref_chars if ref_chars else float('nan'))
+        if per_sample:
+            res['distances'] = dist.view(-1).cpu().numpy()
+        return res
+
+    def decode_mbr(self, data, seq_len, candidates=16, beam_width=100):
+        """Minimum-Bayes-risk decoding under the edit distance, from one forward pass: the `candidates` best prefixes of the CTC prefix search
+        (ops.ctc_beam_nbest, blank 0, merge_repeated=False) are scored exactly (ops.ctc_score per sample, as decode_nbest_beam(rescore=True)),
+        ops.edit_distance compares them with each other and ops.mbr_select picks the one with the least expected distance to the others under
+        their posterior within the list.  Only O(N * candidates) values leave the device.  -> per sample (labels, expected_edits, log_post) of
+        the selected candidate, log_post = -cost - log_norm; ([], inf, -inf) where no candidate is valid.  1 <= candidates <= beam_width <= 128."""
+        candidates, beam_width = int(candidates), int(beam_width)
+        if not (1 <= candidates <= beam_width <= ops.MBR_MAX_K):
+            raise ValueError('decode_mbr takes 1 <= candidates <= beam_width <= %d (got candidates = %d, beam_width = %d)'
+                             % (ops.MBR_MAX_K, candidates, beam_width))
+        logits = self.forward(data, seq_len)
+        sp_len = self.plan(data.shape[0], data.shape[1]).seq_len
+        paths, lens, _, _ = ops.ctc_beam_nbest(logits, sp_len, candidates, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0)
+        width = max(min(int(paths.shape[2]), self.SCORE_MAX_LABEL_LEN), 1)
+        costs, _, _, log_norm = ops.ctc_score(logits, sp_len, paths[:, :, :width].contiguous(), lens, blank=0, per_sample=True)
+        dist = ops.edit_distance(paths, lens, paths, lens)
+        _, best, best_risk = ops.mbr_select(dist, costs)
+        pick = best.clamp(min=0).long()
+        rows = torch.arange(paths.shape[0], device=paths.device)
+        sel_paths, sel_len, sel_cost = paths[rows, pick], lens[rows, pick], costs[rows, pick]
+        best, best_risk, sel_paths, sel_len, sel_cost, log_norm = (v.cpu().numpy() for v in (best, best_risk, sel_paths, sel_len, sel_cost, log_norm))
+        return [([int(v) for v in sel_paths[n, :sel_len[n]]], float(best_risk[n]), float(np.float32(-sel_cost[n]) - log_norm[n]))
+                if best[n] >= 0 else ([], float('inf'), float('-inf')) for n in range(paths.shape[0])]
+
     @staticmethod
     def _spans_of(strings, start, end, score, path_cost):
         """Per sample the list of (label, start_frame, end_frame, confidence) of its string from ops.ctc_align's results (host arrays);

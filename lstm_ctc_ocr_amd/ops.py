@@ -284,6 +284,98 @@ def ctc_align(acts, input_lengths, labels, label_lengths, blank=0, shared=False,
     return start, end, score, path_cost
 
 
+def edit_distance_supported(Ka, Kb, N):
+    """Up to 65536 strings a side, 65535 samples and 2^30 pairs in all (host arithmetic only)."""
+    return bool(nat.lib().ocr_edit_distance_supported(int(Ka), int(Kb), int(N)))
+
+
+def _edit_operand(name, s, s_len, shared):
+    """-> (K, N or None for a shared list, pitch, sample stride in ints) of one side of edit_distance, checked."""
+    want = 2 if shared else s.dim()
+    if s.dtype != torch.int32 or s_len.dtype != torch.int32 or s.dim() != want or s.dim() not in (2, 3) or \
+            tuple(s.shape[:-1]) != tuple(s_len.shape) or not s_len.is_contiguous() or s.device != s_len.device:
+        raise ValueError('%s: int32 %s strings with contiguous int32 lengths of the leading shape (got %s %s / %s %s)'
+                         % (name, '[K, L] (shared)' if shared else '[N, L] or [N, K, L]', s.dtype, tuple(s.shape), s_len.dtype, tuple(s_len.shape)))
+    L = int(s.shape[-1])
+    if (L > 1 and s.stride(-1) != 1) or any(st < 0 for st in s.stride()):
+        raise ValueError('%s: the last dimension must be contiguous and no stride negative (strides %s)' % (name, tuple(s.stride())))
+    if s.shape[0] < 1 or s.shape[-2] < 1:
+        raise ValueError('%s: no strings (shape %s)' % (name, tuple(s.shape)))
+    K = int(s.shape[-2]) if (shared or s.dim() == 3) else 1
+    rows = s.dim() == 3 or shared                       # the K axis is a dimension of the tensor: its stride is the pitch
+    ld = int(s.stride(-2)) if (rows and K > 1) else L
+    if ld < L:
+        raise ValueError('%s: strings overlap (row stride %d below their %d columns)' % (name, ld, L))
+    if shared:
+        return K, None, ld, 0
+    N = int(s.shape[0])
+    sn = int(s.stride(0)) if N > 1 else max(K * ld, 1)
+    if sn == 0:
+        raise ValueError('%s: a sample stride of 0 is a shared list: pass it as [K, L] with shared_%s=True' % (name, name))
+    return K, N, ld, sn
+
+
+def edit_distance(a, a_len, b, b_len, ignore=None, shared_a=False, shared_b=False, want_counts=False):
+    """Levenshtein distances (unit costs) of every string of a against every string of b, per sample.  Each side is int32 [N, L] with lengths
+    [N] (one string per sample), [N, K, L] with lengths [N, K], or with shared_*=True [K, L] with lengths [K] for every sample; the last
+    dimension contiguous, the pitches taken from the strides (a slice of the n-best paths goes in as it is).  ignore: a class dropped from both
+    strings before comparing (None: nothing is).  -> dist int32 [N, Ka, Kb], -1 for every pair with a "no string" (a length below 0 or above
+    the pitch, or more than 255 characters counted); with want_counts also (a_count, b_count), int32 shaped like the lengths: the counted
+    lengths, -1 for "no string"."""
+    Ka, Na, a_ld, a_sn = _edit_operand('a', a, a_len, shared_a)
+    Kb, Nb, b_ld, b_sn = _edit_operand('b', b, b_len, shared_b)
+    if Na is not None and Nb is not None and Na != Nb:
+        raise ValueError('a holds %d samples, b %d' % (Na, Nb))
+    N = Na if Na is not None else Nb if Nb is not None else 1
+    if not edit_distance_supported(Ka, Kb, N):
+        raise ValueError('edit_distance takes 1 <= N <= 65535, 1 <= Ka, Kb <= 65536 and N * Ka * Kb <= 2^30 (got N = %d, Ka = %d, Kb = %d)' % (N, Ka, Kb))
+    _dev(a)
+    _dev(b)
+    dist = torch.empty((N, Ka, Kb), dtype=torch.int32, device=a.device)
+    a_count = torch.empty_like(a_len) if want_counts else None
+    b_count = torch.empty_like(b_len) if want_counts else None
+    # (strings of no columns have no storage: any non-NULL address does, no word of it is read)
+    call("ocr_edit_distance", ptr(a) if a.numel() else ptr(a_len), ptr(a_len), a_ld, a_sn, Ka, ptr(b) if b.numel() else ptr(b_len), ptr(b_len),
+         b_ld, b_sn, Kb, N, -1 if ignore is None else int(ignore), ptr(dist), ptr(a_count), ptr(b_count), _st())
+    return (dist, a_count, b_count) if want_counts else dist
+
+
+def edit_stats(dist, ref_count):
+    """-> int64 [4] on the device: {sum of dist, sum of ref_count, number with dist == 0, number counted} over the pairs with dist >= 0;
+    dist and ref_count contiguous int32 of the same number of elements (ref_count: the reference's counted length of each pair)."""
+    if dist.dtype != torch.int32 or ref_count.dtype != torch.int32 or dist.numel() != ref_count.numel() or dist.numel() < 1 or \
+            not dist.is_contiguous() or not ref_count.is_contiguous():
+        raise ValueError('edit_stats takes contiguous int32 dist and ref_count of one size (got %s %s / %s %s)'
+                         % (dist.dtype, tuple(dist.shape), ref_count.dtype, tuple(ref_count.shape)))
+    _dev(dist)
+    stats = torch.empty(4, dtype=torch.int64, device=dist.device)
+    call("ocr_edit_stats", ptr(dist), ptr(ref_count), dist.numel(), ptr(stats), _st())
+    return stats
+
+
+MBR_MAX_K = 128
+
+
+def mbr_select(dist, costs):
+    """Minimum-Bayes-risk selection: dist int32 [N, K, K], costs f32 [N, K] (minus log-probabilities), both contiguous, K <= 128.
+    -> (risk f32 [N, K], the expected distance of each candidate to the others under their posterior within the list, +inf for a candidate
+    that is not valid (cost not finite or dist[n, i, i] < 0); best int32 [N], the arg-min under (risk, cost, index), -1 where none is valid;
+    best_risk f32 [N])."""
+    if dist.dim() != 3 or costs.dim() != 2 or dist.dtype != torch.int32 or costs.dtype != F32 or dist.shape[1] != dist.shape[2] or \
+            tuple(dist.shape[:2]) != tuple(costs.shape) or not dist.is_contiguous() or not costs.is_contiguous():
+        raise ValueError('mbr_select takes contiguous int32 dist [N, K, K] and float32 costs [N, K] (got %s %s / %s %s)'
+                         % (dist.dtype, tuple(dist.shape), costs.dtype, tuple(costs.shape)))
+    N, K = int(costs.shape[0]), int(costs.shape[1])
+    if not (1 <= K <= MBR_MAX_K and 1 <= N <= 65535):
+        raise ValueError('mbr_select takes 1 <= K <= %d candidates of 1 <= N <= 65535 samples (got K = %d, N = %d)' % (MBR_MAX_K, K, N))
+    _dev(dist)
+    risk = torch.empty((N, K), dtype=F32, device=dist.device)
+    best = torch.empty(N, dtype=torch.int32, device=dist.device)
+    best_risk = torch.empty(N, dtype=F32, device=dist.device)
+    call("ocr_mbr_select", ptr(dist), ptr(costs), N, K, ptr(risk), ptr(best), ptr(best_risk), _st())
+    return risk, best, best_risk
+
+
 def ctc_greedy_decode(acts, input_lengths, blank=0, pad_value=0):
     T, N, C = acts.shape
     out = torch.empty((N, T), dtype=torch.int32, device=acts.device)
