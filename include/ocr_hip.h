@@ -101,6 +101,13 @@ int ocr_ctc_score_workspace_size(int alphabet_size, int max_time, int minibatch,
 int ocr_ctc_score(const float* activations, const int* input_lengths, const int* cand_labels, const int* cand_lengths, int sample_stride,
                   int alphabet_size, int minibatch, int max_time, int num_candidates, int max_label_len, int blank_label,
                   float* costs, int* best, float* best_cost, float* log_norm, void* workspace, size_t workspace_bytes, void* stream);
+/* Shallow fusion of scored candidates: costs[n][k] -= lm_score[n][k] in place (both f32 [minibatch, num_candidates], contiguous; lm_score is
+ * what a language model or constraint adds to the candidate's log-probability, as ocr_ctc_beam_decode_lm returns it; +inf - (-inf) is +inf,
+ * so "no string" stays "no string"), then best / best_cost / log_norm of the fused costs exactly as ocr_ctc_score computes them - with
+ * lm_score all zero the costs keep their bits and the three outputs are ocr_ctc_score's.  1 <= minibatch <= 65535,
+ * 1 <= num_candidates <= 65536, no operand NULL; anything else is OCR_STATUS_INVALID and nothing is launched. */
+int ocr_ctc_score_fuse(float* costs, const float* lm_score, int minibatch, int num_candidates, int* best, float* best_cost, float* log_norm,
+                       void* stream);
 /* lexicon scoring on a prefix tree: the costs, best, best_cost and log_norm of ocr_ctc_score for ONE lexicon shared by every sample, of up to
  * 1048576 words (ocr_ctc_trie_supported: 1 <= alphabet_size <= 16384, max_time >= 1, 1 <= num_words <= 1048576; arithmetic only).  Every node
  * of the lexicon's prefix tree runs the alpha recursion of its label slot and of the blank slot behind it once, whatever the number of words
@@ -240,6 +247,32 @@ int ocr_ctc_beam_decode_nbest(const float* activations, const int* input_lengths
                               int max_time, int beam_width, int top_paths, int blank, int merge_repeated, int pad_value,
                               int* decoded, int* decoded_lengths, float* neg_log_prob, int* count, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* The prefix search of ocr_ctc_beam_decode_nbest (any blank, no merge_repeated) fused with a deterministic weighted automaton over the
+ * labels - a language model or a constraint inside the search, not after it.  The automaton has num_states states, start state 0 and
+ *   lm_next: int32 [num_states, alphabet_size], lm_weight: f32 [num_states, alphabet_size], lm_final: f32 [num_states],
+ * row-major and indexed by the caller's class ids; the blank's column is ignored.  Extending a prefix in state s by class c pays
+ * lm_weight[s][c] and moves to lm_next[s][c]; the transition is forbidden (never a candidate, never a node) when the weight is not
+ * finite (-inf, +inf, NaN) or lm_next[s][c] lies outside [0, num_states) - every entry is bounds-checked, no table content makes the
+ * kernel read outside the tables.  The search keeps, prunes and ranks by
+ *   total(P) = log p_beam(P | activations) + W(P),   W(P) = sum of the weights along P,
+ * and the final ranking adds lm_final[state(P)]: a prefix whose lm_final is not finite may not end there and is not returned.
+ *   decoded, decoded_lengths, count: as ocr_ctc_beam_decode_nbest; neg_log_prob: f32 [minibatch, top_paths] = -(total + lm_final);
+ *   lm_score: f32 [minibatch, top_paths] = W(P) + lm_final, so -neg_log_prob - lm_score is the beam's acoustic log-probability of the
+ *   string (comparable with ocr_ctc_score).  Slots at and beyond count[n] (which may be 0: the automaton can refuse everything) hold
+ *   pad_value / -1 / +inf, and lm_score -inf.
+ * Supported (ocr_ctc_beam_lm_supported, host-only, 1 / 0): 1 <= beam_width <= 128, 1 <= num_states <= 1048576, and the table kernel's LDS
+ * (see ocr_ctc_beam_decode) plus 2048 bytes <= 160 KB: alphabet_size <= 256 at beam_width 100, <= 200 at 128.  The workspace
+ * (ocr_ctc_beam_lm_workspace_size) is larger than ocr_ctc_beam_workspace_size's: each node also holds its state and its weight.
+ * 1 <= top_paths <= beam_width, 0 <= blank < alphabet_size, none of the operands may be NULL; anything else is OCR_STATUS_INVALID,
+ * nothing is launched and no output is written.  With one state, weights 0 and final 0 the outputs are ocr_ctc_beam_decode_nbest's
+ * (merge_repeated = 0) bit for bit and lm_score is 0. */
+int ocr_ctc_beam_lm_supported(int alphabet_size, int beam_width, int num_states);
+int ocr_ctc_beam_lm_workspace_size(int alphabet_size, int minibatch, int max_time, int beam_width, size_t* bytes);
+int ocr_ctc_beam_decode_lm(const float* activations, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
+                           int beam_width, int top_paths, int blank, int pad_value,
+                           const int* lm_next, const float* lm_weight, const float* lm_final, int num_states,
+                           int* decoded, int* decoded_lengths, float* neg_log_prob, float* lm_score, int* count,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* Which kernel ocr_ctc_beam_decode runs for a shape - a host-only query like ocr_conv3x3_kernel_choice (nothing is launched, works
  * without a GPU): 0 refused, 1 table kernel, 2 wide kernel.  It honours ocr_set_beam_engine. */
 int ocr_ctc_beam_kernel_choice(int alphabet_size, int beam_width);

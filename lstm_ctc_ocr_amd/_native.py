@@ -37,6 +37,7 @@ _SIGS = {
     "ocr_ctc_score_supported": ([_I, _I, _I, _I], _I),
     "ocr_ctc_score_workspace_size": ([_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_score": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "ocr_ctc_score_fuse": ([_P, _P, _I, _I, _P, _P, _P, _P], _I),
     "ocr_ctc_trie_chunk_capacity": ([], _I),
     "ocr_ctc_trie_supported": ([_I, _I, _I], _I),
     "ocr_ctc_trie_build": ([_P, _P, _I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _P, _P, _P, _P], _I),
@@ -57,6 +58,9 @@ _SIGS = {
     "ocr_ctc_beam_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_beam_decode": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "ocr_ctc_beam_decode_nbest": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "ocr_ctc_beam_lm_supported": ([_I, _I, _I], _I),
+    "ocr_ctc_beam_lm_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
+    "ocr_ctc_beam_decode_lm": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
     "ocr_ctc_beam_kernel_choice": ([_I, _I], _I),
     "ocr_set_beam_engine": ([_I], _I),
     "ocr_gemm_nt_bf16": ([_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P], _I),

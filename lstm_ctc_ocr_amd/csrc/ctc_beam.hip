@@ -31,8 +31,20 @@
 // class order, so candidates keep the relative order of b*C + c and the tie rule of step (e) is the table kernel's.  The in-beam
 // question is answered without a table: each beam entry whose parent is in the beam looks its own label up in S (binary search) and
 // cancels that one candidate.  LDS: 4*C + 4*(K + K*M) + 4*M bytes plus the beam arrays, 136 KB at C = 16384, K = 128.
+//
+// LM = true (table kernel only) is ocr_ctc_beam_decode_lm: the search is steered by a deterministic weighted automaton over the labels
+// (next[state][class], weight[state][class], final[state]; -inf = forbidden).  Every alignment that collapses to a prefix P holds the same
+// characters, so the fused score factorises exactly: total(P) = log p_beam(P) + W(P), W(P) the sum of the weights along P's state sequence.
+// The state is a function of the prefix, so it lives on the prefix's node: node_state / node_w (the weight the last character paid) are
+// written once where step (f) allocates the node, and a prefix that re-enters the beam on its old node finds them there.  New children pay
+// their weight in step (c), the mass an in-beam child takes from its in-beam parent pays the child's node_w in step (b), the repeat term
+// pnb[s] and the blank term pay nothing.  Pruning ranks by total; the final ranking adds final[state].  A transition is forbidden when its
+// weight is not finite or its next state lies outside [0, num_states): every state the kernel holds is in range, so no table content
+// makes it read outside the tables.
 #include "common.h"
+#include <float.h>
 #include <math.h>
+#include <type_traits>
 
 #define BEAM_MAX 128
 #define BEAM_WIDE_MAX_C 16384        // the wide kernel's promise: 2 <= C <= 16384 for every K <= BEAM_MAX (node_label is a short)
@@ -56,6 +68,13 @@ struct BeamArgs {
     int* node_parent; short* node_label; int* node_slot;     // per sample: T*K + 2 entries
     int blank, top_paths; int* count;                        // n-best entry only (NBEST = true)
 };
+// the fused entry's operands ride behind the others, so the instances without LM keep their kernel arguments
+struct BeamLmArgs : BeamArgs {
+    const int* lm_next; const float* lm_weight; const float* lm_final; int num_states;      // [H][C], [H][C], [H]: the caller's class ids
+    int* node_state; float* node_w;                          // per sample: T*K + 2 entries, beside node_parent / node_label / node_slot
+    float* lm_score;
+};
+__device__ __forceinline__ bool lm_finite(float w) { return fabsf(w) <= FLT_MAX; }       // false for -inf, +inf and NaN
 
 // NBEST = true is ocr_ctc_beam_decode_nbest: the caller's blank is any class and the `top_paths` best leaves are emitted.  Inside the
 // kernel the blank stays the LAST class: the log-softmax row is stored through the monotone re-indexing  k -> k (k < blank),
@@ -63,8 +82,11 @@ struct BeamArgs {
 // non-blank classes, so every "lowest class index" / "lowest candidate index" tie rule picks the class it would pick in the caller's
 // numbering, and for blank == C - 1 it is the identity.  NBEST = false is ocr_ctc_beam_decode as it always was (no re-indexing in its
 // instances, thread 0 emits the best leaf).
-template <bool WIDE, bool NBEST>
-__global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
+// LM = true is ocr_ctc_beam_decode_lm (see the header): NBEST's re-indexing and emission, the automaton's terms in steps (b), (c), (f) and in
+// the final ranking.  Its tables are indexed by the caller's class ids: internal class c is the caller's  c < blank ? c : c + 1.
+template <bool WIDE, bool NBEST, bool LM = false>
+__global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<LM, BeamLmArgs, BeamArgs> a) {
+    static_assert(!LM || (NBEST && !WIDE), "the fused search runs on the table kernel with the n-best emission");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = a.C, K = a.K, blank = C - 1;
@@ -87,6 +109,10 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     float* b_pnb = b_pb + 2 * BEAM_MAX;
     float* b_tot = b_pnb + 2 * BEAM_MAX;
     int* sel_src = (int*)(b_tot + 2 * BEAM_MAX);          // [BEAM_MAX] candidate index of each new slot
+    int* b_state = sel_src + BEAM_MAX;                    // LM: automaton state after the entry's prefix, two generations
+    float* b_w = (float*)(b_state + 2 * BEAM_MAX);        // LM: weight the prefix's last character paid (node_w)
+    int* nstate = nullptr; float* nw = nullptr;
+    if constexpr (LM) { nstate = a.node_state + (size_t)n * pool; nw = a.node_w + (size_t)n * pool; }
     __shared__ int s_cnt[4];
     __shared__ unsigned s_key;
     __shared__ int s_misc[4];
@@ -95,6 +121,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
     if (tid == 0) {
         b_node[0] = 0; b_last[0] = -1; b_ps[0] = -1; b_pb[0] = 0.f; b_pnb[0] = NEGINF; b_tot[0] = 0.f;
         npar[0] = -1; nlab[0] = -1; nslot[0] = 0;
+        if constexpr (LM) { b_state[0] = 0; b_w[0] = 0.f; nstate[0] = 0; nw[0] = 0.f; }
         s_misc[0] = 1;        // beam size
         s_misc[1] = 1;        // nodes allocated
     }
@@ -105,6 +132,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         const int nb = s_misc[0];
         int* node = b_node + gen * BEAM_MAX; int* last = b_last + gen * BEAM_MAX; int* ps = b_ps + gen * BEAM_MAX;
         float* pb = b_pb + gen * BEAM_MAX; float* pnb = b_pnb + gen * BEAM_MAX; float* tot = b_tot + gen * BEAM_MAX;
+        int* state = b_state + gen * BEAM_MAX; float* wlast = b_w + gen * BEAM_MAX;      // (LM only)
         // (a) log-softmax of the frame
         const float* row = a.act + ((size_t)t * a.N + n) * C;
         {
@@ -183,7 +211,11 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             if (last[s] >= 0) {
                 nl = pnb[s];
                 const int p = ps[s];
-                if (p >= 0) nl = blse(nl, (last[s] == last[p]) ? pb[p] : tot[p]);
+                if constexpr (LM) {
+                    if (p >= 0) nl = blse(nl, ((last[s] == last[p]) ? pb[p] : tot[p]) + wlast[s]);     // the parent's mass pays this character's weight
+                } else {
+                    if (p >= 0) nl = blse(nl, (last[s] == last[p]) ? pb[p] : tot[p]);
+                }
                 if (nl != NEGINF) nl += lp[last[s]];
             }
             my_npnb = nl;
@@ -197,7 +229,15 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
                 float v = NEGINF;
                 if (c != blank && table[b * C + c] < 0) {
                     const float prev = (c == last[b]) ? pb[b] : tot[b];
-                    if (prev != NEGINF) v = prev + lp[c];
+                    if constexpr (LM) {
+                        // state[b] < num_states and the caller's class id < C: inside the tables whatever they hold
+                        const size_t e = (size_t)state[b] * C + (c < a.blank ? c : c + 1);
+                        const float w = a.lm_weight[e];
+                        const unsigned nx = (unsigned)a.lm_next[e];
+                        if (prev != NEGINF && lm_finite(w) && nx < (unsigned)a.num_states) v = prev + lp[c] + w;
+                    } else {
+                        if (prev != NEGINF) v = prev + lp[c];
+                    }
                 }
                 cand[nb + i] = v;
             }
@@ -276,6 +316,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         // leaves' new (p_blank, p_label) live in registers of thread s; publish them through the dead half of the beam arrays
         if (tid < nb) { pb2[tid] = my_npb; pnb2[tid] = my_npnb; }     // temporarily indexed by OLD slot
         float r_pb = NEGINF, r_pnb = NEGINF, r_tot = NEGINF; int r_node = -1, r_last = -1, r_src = -1;
+        int r_state = 0; float r_w = 0.f;
         if (tid < nnew) { r_src = sel_src[tid]; r_tot = cand[r_src]; }
         __syncthreads();
         // One node per prefix: a child that enters the beam may be a prefix that was in it before (see the header).  Its node is found by
@@ -308,12 +349,20 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             const int i = r_src;
             if (i < nb) {                                   // surviving leaf
                 r_node = node[i]; r_last = last[i]; r_pb = pb2[i]; r_pnb = pnb2[i];
+                if constexpr (LM) { r_state = state[i]; r_w = wlast[i]; }
             } else {                                        // child of leaf b with label c: back on its old node, or new
                 const int b = (i - nb) / M, c = WIDE ? sel_cls[(i - nb) - b * M] : (i - nb) - b * M;
                 int id = sel_src[tid];
                 if (id < 0) {
                     id = atomicAdd(&s_misc[1], 1);
                     npar[id] = node[b]; nlab[id] = (short)c;
+                    if constexpr (LM) {                     // admitted, so step (c) found the weight finite and the next state in range
+                        const size_t e = (size_t)state[b] * C + (c < a.blank ? c : c + 1);
+                        r_state = a.lm_next[e]; r_w = a.lm_weight[e];
+                        nstate[id] = r_state; nw[id] = r_w;
+                    }
+                } else if constexpr (LM) {                  // back on its old node: the state and the weight it was given then
+                    r_state = nstate[id]; r_w = nw[id];
                 }
                 r_node = id; r_last = c; r_pb = NEGINF; r_pnb = r_tot;
             }
@@ -322,6 +371,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         if (tid < nnew) {
             node2[tid] = r_node; last2[tid] = r_last; pb2[tid] = r_pb; pnb2[tid] = r_pnb; tot2[tid] = r_tot;
             nslot[r_node] = tid;
+            if constexpr (LM) { (b_state + g2 * BEAM_MAX)[tid] = r_state; (b_w + g2 * BEAM_MAX)[tid] = r_w; }
         }
         if constexpr (!WIDE) for (int i = tid; i < K * C; i += 256) table[i] = -1;
         __syncthreads();
@@ -341,6 +391,15 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
         // entries ahead of it.  -inf totals are never returned (they rank behind every finite one, so they do not disturb the counts).
         const int nb = s_misc[0], P = a.top_paths, ub = a.blank;
         const float* tot = b_tot + gen * BEAM_MAX; const int* node = b_node + gen * BEAM_MAX;
+        if constexpr (LM) {                                  // ranked by total + final[state]; a state that may not end the string is -inf
+            float* key = (float*)smem_raw + ((C + 3) & ~3);     // cand is dead
+            if (tid < nb) {
+                const float f = a.lm_final[(b_state + gen * BEAM_MAX)[tid]];
+                key[tid] = lm_finite(f) ? tot[tid] + f : NEGINF;
+            }
+            __syncthreads();
+            tot = key;
+        }
         int valid = 0;
         for (int s = 0; s < nb; ++s) valid += (tot[s] != NEGINF);
         const int cnt = min(valid, P);
@@ -351,7 +410,11 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             if (rank < P) {                                  // this thread walks its own path root-ward
                 int* o = a.out + ((size_t)n * P + rank) * a.T;
                 int len = 0;
-                for (int id = node[tid]; id > 0; id = npar[id]) { const int c = nlab[id]; o[len++] = (c < ub) ? c : c + 1; }      // reversed
+                float lmw = 0.f;                              // LM: W(P), the weights along the path
+                for (int id = node[tid]; id > 0; id = npar[id]) {                                                                 // reversed
+                    const int c = nlab[id]; o[len++] = (c < ub) ? c : c + 1;
+                    if constexpr (LM) lmw += nw[id];
+                }
                 for (int i = 0; i < len / 2; ++i) { int tmp = o[i]; o[i] = o[len - 1 - i]; o[len - 1 - i] = tmp; }
                 if (a.merge_repeated) {
                     int w = 0;
@@ -361,6 +424,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
                 for (int i = len; i < a.T; ++i) o[i] = a.pad_value;
                 a.out_len[(size_t)n * P + rank] = len;
                 a.neg_log_prob[(size_t)n * P + rank] = -mine;
+                if constexpr (LM) a.lm_score[(size_t)n * P + rank] = lmw + a.lm_final[(b_state + gen * BEAM_MAX)[tid]];
             }
         }
         if (tid >= cnt && tid < P) {                         // no path for these slots (P <= 128 < 256 threads)
@@ -368,6 +432,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(BeamArgs a) {
             for (int i = 0; i < a.T; ++i) o[i] = a.pad_value;
             a.out_len[(size_t)n * P + tid] = -1;
             a.neg_log_prob[(size_t)n * P + tid] = INFINITY;
+            if constexpr (LM) a.lm_score[(size_t)n * P + tid] = NEGINF;
         }
         if (tid == 0) a.count[n] = cnt;
         return;
@@ -404,6 +469,11 @@ static size_t beam_wide_lds_bytes(int C, int K) {
     size_t b = (size_t)((C + 3) & ~3) * 4 + ((size_t)K + (size_t)K * M) * 4 + M * 4 + (size_t)BEAM_MAX * 2 * 6 * 4 + (size_t)BEAM_MAX * 4;
     return (b + 15) & ~(size_t)15;
 }
+
+static size_t beam_lm_lds_bytes(int C, int K) {          // the table kernel's, and b_state / b_w: two more [2][BEAM_MAX] arrays
+    return beam_lds_bytes(C, K) + (size_t)BEAM_MAX * 2 * 2 * 4;
+}
+#define BEAM_LM_MAX_STATES (1 << 20)
 
 static int g_beam_engine = 0;
 extern "C" int ocr_set_beam_engine(int engine) {       // A/B + test knob: 0 = table kernel where it fits, 2 = wide kernel wherever it covers
@@ -482,4 +552,49 @@ extern "C" int ocr_ctc_beam_decode_nbest(const float* activations, const int* in
                   decoded, decoded_lengths, neg_log_prob, nullptr, nullptr, nullptr, blank, top_paths, count};
     beam_workspace(a, workspace);
     return beam_launch<true>(a, stream);
+}
+
+// ---- the search fused with a label automaton (LM = true; the table kernel only)
+extern "C" int ocr_ctc_beam_lm_supported(int alphabet_size, int beam_width, int num_states) {
+    if (alphabet_size < 2 || beam_width < 1 || beam_width > BEAM_MAX || num_states < 1 || num_states > BEAM_LM_MAX_STATES) return 0;
+    return beam_lm_lds_bytes(alphabet_size, beam_width) <= BEAM_LDS_LIMIT ? 1 : 0;
+}
+// node_parent, node_slot, node_state (int), node_w (float), node_label (short) per pool entry
+extern "C" int ocr_ctc_beam_lm_workspace_size(int alphabet_size, int minibatch, int max_time, int beam_width, size_t* bytes) {
+    if (!bytes || minibatch <= 0 || max_time <= 0 || !ocr_ctc_beam_lm_supported(alphabet_size, beam_width, 1)) return OCR_ERR_INVALID;
+    const size_t pool = (size_t)max_time * beam_width + 2;
+    *bytes = (size_t)minibatch * pool * (sizeof(int) * 3 + sizeof(float) + sizeof(short));
+    *bytes = (*bytes + 255) & ~(size_t)255;
+    return OCR_OK;
+}
+// The top_paths best prefixes under total(P) + final[state(P)], best first; neg_log_prob = -(that sum), lm_score = W(P) + final, so
+// -neg_log_prob - lm_score is the beam's acoustic log-probability.  Outputs as ocr_ctc_beam_decode_nbest's, lm_score -inf beyond count[n].
+extern "C" int ocr_ctc_beam_decode_lm(const float* activations, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
+                                      int beam_width, int top_paths, int blank, int pad_value, const int* lm_next, const float* lm_weight,
+                                      const float* lm_final, int num_states, int* decoded, int* decoded_lengths, float* neg_log_prob,
+                                      float* lm_score, int* count, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    size_t need = 0;
+    if (!activations || !input_lengths || !lm_next || !lm_weight || !lm_final || !decoded || !decoded_lengths || !neg_log_prob || !lm_score ||
+        !count || !workspace)
+        return OCR_ERR_INVALID;
+    if (!ocr_ctc_beam_lm_supported(alphabet_size, beam_width, num_states)) return OCR_ERR_INVALID;
+    if (ocr_ctc_beam_lm_workspace_size(alphabet_size, minibatch, max_time, beam_width, &need) != OCR_OK || workspace_bytes < need)
+        return OCR_ERR_INVALID;
+    if (top_paths < 1 || top_paths > beam_width || blank < 0 || blank >= alphabet_size) return OCR_ERR_INVALID;
+    BeamLmArgs a;
+    (BeamArgs&)a = {activations, input_lengths, max_time, minibatch, alphabet_size, beam_width, 0, pad_value,
+                    decoded, decoded_lengths, neg_log_prob, nullptr, nullptr, nullptr, blank, top_paths, count};
+    const size_t pool = (size_t)max_time * beam_width + 2, all = (size_t)minibatch * pool;
+    a.node_parent = (int*)workspace;
+    a.node_slot = a.node_parent + all;
+    a.node_state = a.node_slot + all;
+    a.node_w = (float*)(a.node_state + all);
+    a.node_label = (short*)(a.node_w + all);
+    a.lm_next = lm_next; a.lm_weight = lm_weight; a.lm_final = lm_final; a.num_states = num_states; a.lm_score = lm_score;
+    const size_t lds = beam_lm_lds_bytes(alphabet_size, beam_width);
+    if (ocr_allow_lds<ctc_beam_kernel<false, true, true>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
+    ctc_beam_kernel<false, true, true><<<minibatch, 256, lds, stream>>>(a);
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
 }

@@ -160,3 +160,23 @@ extern "C" int ocr_ctc_score(const float* activations, const int* input_lengths,
     }
     return OCR_OK;
 }
+
+// Shallow fusion after the fact: costs[n][k] -= lm_score[n][k] in place (a candidate's CTC cost minus what a language model or constraint
+// adds to its log-probability; an empty slot is +inf - (-inf) = +inf), then best / best_cost / log_norm of the fused costs as ocr_ctc_score
+// computes them.  With lm_score all zero the costs keep their bits and the three outputs are ocr_ctc_score's.
+__global__ __launch_bounds__(256) void ctc_score_fuse_kernel(float* __restrict__ costs, const float* __restrict__ lm_score, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) costs[i] = costs[i] - lm_score[i];
+}
+extern "C" int ocr_ctc_score_fuse(float* costs, const float* lm_score, int minibatch, int num_candidates, int* best, float* best_cost,
+                                  float* log_norm, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!costs || !lm_score || !best || !best_cost || !log_norm) return OCR_ERR_INVALID;
+    if (minibatch < 1 || minibatch > 65535 || num_candidates < 1 || num_candidates > SCORE_MAX_K) return OCR_ERR_INVALID;
+    const size_t total = (size_t)minibatch * num_candidates;
+    ctc_score_fuse_kernel<<<(unsigned)((total + 255) / 256), 256, 0, stream>>>(costs, lm_score, total);
+    OCR_CHECK_LAUNCH();
+    ctc_score_best(costs, minibatch, num_candidates, best, best_cost, log_norm, stream);
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}

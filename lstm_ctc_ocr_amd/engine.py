@@ -25,6 +25,7 @@ from . import ops
 from ._native import NativeError, call as nat_call
 from .engine_ops import (BF16, F32, I32, _env, _number, _switch, _AddOp, _AvgPoolOp, _BatchNormOp, _BiLstmOp, _ConcatOp, _ConvOp,
                          _Conv3x3Op, _DropoutOp, _FcOp, _InputOp, _PoolOp, _ReluOp, _SoftmaxOp, _SubsampleOp, _ViewOp, _conv_op)
+from .automaton import LabelAutomaton
 from .lexicon import LexiconTrie
 from .layout import FlatLayout, execution_order, init_host_parameters
 
@@ -932,9 +933,28 @@ class Engine(object):
                           (network.py:656-657, training.py:32).
         method='greedy' : best path with blank 0.
         method='prefix' : the textbook CTC prefix search: the same beam search with blank 0 and merge_repeated=False.  Its prefixes are label
-                          strings (no zero occurs in them); not the reference's decoder.
+                          strings (no zero occurs in them); not the reference's decoder.  decode_lm is this search fused with a language
+                          model or a constraint.
         method='lexicon': the likeliest string of `lexicon` (label lists, blank 0, or a lexicon.LexiconTrie built with blank 0) under CTC; [] for a
                           sample none of them fits.  With a LexiconTrie only the arg-min leaves the device, not the N x K cost matrix."""
+        return self._decode(data, seq_len, method, beam_width, lexicon, None)
+
+    def decode_lm(self, data, seq_len, lm, beam_width=100):
+        """decode(method='prefix') with the search fused with `lm`, an automaton.LabelAutomaton over the classes (blank 0): a language model
+        (LabelAutomaton.from_ngram) or a constraint (from_lexicon, from_pattern) steers the beam itself (ops.ctc_beam_lm) where
+        rescoring.rerank only re-orders what the acoustic beam kept.  -> the best string per sample under log p_beam + automaton.score; [] for
+        a sample for which the automaton accepts nothing in the beam.  (A method of its own: decode's signature is pinned.)"""
+        return self._decode(data, seq_len, 'prefix', beam_width, None, self._check_lm(lm))
+
+    @staticmethod
+    def _check_lm(lm):
+        if not isinstance(lm, LabelAutomaton):
+            raise ValueError('lm must be an automaton.LabelAutomaton (got %s)' % type(lm).__name__)
+        if lm.blank != 0:
+            raise ValueError('blank 0, but the LabelAutomaton was built with blank %d' % lm.blank)
+        return lm
+
+    def _decode(self, data, seq_len, method, beam_width, lexicon, lm):
         if method == 'lexicon':
             if lexicon is None:
                 raise ValueError("decode(method='lexicon') needs a lexicon")
@@ -950,13 +970,24 @@ class Engine(object):
         if method == 'greedy':
             out, lens = ops.ctc_greedy_decode(logits, sp.seq_len, blank=0, pad_value=0)
         elif method == 'prefix':
-            paths, plens, _, _ = ops.ctc_beam_nbest(logits, sp.seq_len, 1, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0)
+            paths, plens = self._prefix_search(logits, sp.seq_len, 1, beam_width, lm)[:2]
             out, lens = paths[:, 0], plens[:, 0]
         else:
             out, lens, _ = ops.ctc_beam_decode(logits, sp.seq_len, beam_width=beam_width, merge_repeated=True, pad_value=0)
         out = out.cpu().numpy()
         lens = lens.cpu().numpy()
+        if lm is not None:
+            lens = np.maximum(lens, 0)                    # -1: the automaton accepts nothing in this sample's beam
         return [[int(v) for v in out[i, :lens[i]] if v != 0] for i in range(out.shape[0])]
+
+    @staticmethod
+    def _prefix_search(logits, seq_len, top_paths, beam_width, lm):
+        """The CTC prefix search (blank 0, no merge) on device logits, fused with the automaton `lm` when one is given
+        -> (paths, lengths, neg_log_prob, count, lm_score or None)."""
+        if lm is None:
+            return ops.ctc_beam_nbest(logits, seq_len, top_paths, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0) + (None,)
+        paths, lens, nlp, lm_score, count = ops.ctc_beam_lm(logits, seq_len, lm, top_paths, beam_width=beam_width, blank=0, pad_value=0)
+        return paths, lens, nlp, count, lm_score
 
     SCORE_MAX_LABEL_LEN = 255
 
@@ -1031,6 +1062,17 @@ class Engine(object):
                        list; the order is by exact cost.  A prefix beyond 255 labels has no exact cost and drops out.
         rescore=False: log_prob is the beam's own score (a lower bound: the beam sums a subset of the string's alignments), log_post its
                        normalisation over the returned paths; the order is the beam's."""
+        return self._nbest_beam(data, seq_len, k, beam_width, candidates, rescore, None)
+
+    def decode_nbest_beam_lm(self, data, seq_len, lm, k=5, beam_width=100, candidates=None, rescore=True):
+        """decode_nbest_beam with the search fused with `lm`, an automaton.LabelAutomaton (blank 0): the candidates come from ops.ctc_beam_lm, so
+        only strings the automaton accepts are returned (a sample may get an empty list).  With rescore=True their exact acoustic costs are
+        computed as in decode_nbest_beam and the automaton's score (lm_score) is subtracted on the device (ops.ctc_score_fuse) before
+        ops.ctc_topk selects: log_prob = the exact acoustic log-probability plus automaton.score(labels), log_post is normalised within the
+        candidate list, the logits never leave the device.  With rescore=False log_prob is the fused search's own score."""
+        return self._nbest_beam(data, seq_len, k, beam_width, candidates, rescore, self._check_lm(lm))
+
+    def _nbest_beam(self, data, seq_len, k, beam_width, candidates, rescore, lm):
         k, beam_width = int(k), int(beam_width)
         candidates = k if candidates is None else int(candidates)
         if not (1 <= k <= self.NBEST_MAX_K and k <= candidates <= beam_width):
@@ -1038,10 +1080,13 @@ class Engine(object):
                              % (self.NBEST_MAX_K, k, candidates, beam_width))
         logits = self.forward(data, seq_len)
         sp_len = self.plan(data.shape[0], data.shape[1]).seq_len
-        paths, lens, nlp, count = ops.ctc_beam_nbest(logits, sp_len, candidates, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0)
+        paths, lens, nlp, count, lm_score = self._prefix_search(logits, sp_len, candidates, beam_width, lm)
         if rescore:
             width = max(min(int(paths.shape[2]), self.SCORE_MAX_LABEL_LEN), 1)
             costs, _, _, log_norm = ops.ctc_score(logits, sp_len, paths[:, :, :width].contiguous(), lens, blank=0, per_sample=True)
+            if lm is not None:
+                # fused cost = exact acoustic cost - lm_score, and its normaliser over the candidate list (an empty slot stays +inf)
+                costs, _, _, log_norm = ops.ctc_score_fuse(costs, lm_score)
             index, cost, log_post, count = (v.cpu().numpy() for v in ops.ctc_topk(costs, k, log_norm=log_norm))
             log_prob = -cost
         else:
@@ -1160,6 +1205,14 @@ class Engine(object):
         """decode and align from the same forward pass (the logits stay on the device between the two): -> (strings as decode(method=...) returns
         them, spans as align returns them for those strings).  method 'greedy', 'prefix' or 'lexicon', all with blank 0; the reference's beam
         decoder ('beam') has blank C - 1 and its results are not aligned here."""
+        return self._decode_spans(data, seq_len, method, lexicon, None)
+
+    def decode_spans_lm(self, data, seq_len, lm):
+        """decode_spans(method='prefix') with the search fused with the automaton.LabelAutomaton `lm`, as decode_lm: -> (decode_lm's strings, their
+        spans); a sample for which the automaton accepts nothing has the string [] and no spans."""
+        return self._decode_spans(data, seq_len, 'prefix', None, self._check_lm(lm))
+
+    def _decode_spans(self, data, seq_len, method, lexicon, lm):
         if method not in ('greedy', 'prefix', 'lexicon'):
             raise ValueError("decode_spans takes method 'greedy', 'prefix' or 'lexicon' (got %r)" % (method,))
         if method == 'lexicon' and lexicon is None:
@@ -1171,11 +1224,13 @@ class Engine(object):
             if method == 'greedy':
                 out, lens = ops.ctc_greedy_decode(logits, sp_len, blank=0, pad_value=0)
             else:
-                paths, plens, _, _ = ops.ctc_beam_nbest(logits, sp_len, 1, blank=0, merge_repeated=False, pad_value=0)
+                paths, plens = self._prefix_search(logits, sp_len, 1, 100, lm)[:2]
                 out, lens = paths[:, 0], plens[:, 0].contiguous()
             width = max(min(int(out.shape[1]), self.SCORE_MAX_LABEL_LEN), 1)
             start, end, score, cost = (v.cpu().numpy() for v in ops.ctc_align(logits, sp_len, out[:, :width].contiguous(), lens, blank=0))
             out, lens = out.cpu().numpy(), lens.cpu().numpy()
+            if lm is not None:
+                lens = np.maximum(lens, 0)                # -1: the automaton accepts nothing in this sample's beam (no spans either)
             strings = [[int(v) for v in out[i, :lens[i]] if v != 0] for i in range(out.shape[0])]
             return strings, self._spans_of(strings, start, end, score, cost)
         if isinstance(lexicon, LexiconTrie):

@@ -158,6 +158,22 @@ def ctc_score(acts, input_lengths, lexicon, lexicon_lengths, blank=0, per_sample
     return costs, best, best_cost, log_norm
 
 
+def ctc_score_fuse(costs, lm_score):
+    """Shallow fusion of scored candidates, in place: costs f32 [N, K] (ctc_score's) -= lm_score f32 [N, K] (ctc_beam_lm's), both contiguous.
+    -> (costs, best, best_cost, log_norm) of the fused costs as ctc_score returns them; an empty slot (+inf, -inf) stays +inf."""
+    _dev(costs)
+    if costs.dim() != 2 or costs.shape != lm_score.shape or costs.dtype != F32 or lm_score.dtype != F32 or not costs.is_contiguous() or \
+            not lm_score.is_contiguous():
+        raise ValueError('ctc_score_fuse takes two contiguous float32 [N, K] matrices (got %s %s / %s %s)'
+                         % (costs.dtype, tuple(costs.shape), lm_score.dtype, tuple(lm_score.shape)))
+    N, K = int(costs.shape[0]), int(costs.shape[1])
+    best = torch.empty(N, dtype=torch.int32, device=costs.device)
+    best_cost = torch.empty(N, dtype=F32, device=costs.device)
+    log_norm = torch.empty(N, dtype=F32, device=costs.device)
+    call("ocr_ctc_score_fuse", ptr(costs), ptr(lm_score), N, K, ptr(best), ptr(best_cost), ptr(log_norm), _st())
+    return costs, best, best_cost, log_norm
+
+
 def ctc_trie_supported(C, T, K):
     """C <= 16384 classes, a lexicon of up to 1048576 words (host arithmetic only)."""
     return bool(nat.lib().ocr_ctc_trie_supported(C, T, K))
@@ -419,6 +435,41 @@ def ctc_beam_nbest(acts, input_lengths, top_paths, beam_width=100, blank=None, m
     call("ocr_ctc_beam_decode_nbest", ptr(_dev(acts)), ptr(input_lengths), C, N, T, beam_width, top_paths, blank, int(merge_repeated),
          pad_value, ptr(paths), ptr(lens), ptr(nlp), ptr(count), ptr(workspace), workspace.numel(), _st())
     return paths, lens, nlp, count
+
+
+def ctc_beam_lm_supported(C, K, H):
+    """Whether ctc_beam_lm covers C classes at beam width K with an automaton of H states (host arithmetic only): K <= 128, H <= 1048576 and
+    the table kernel's LDS with two more beam arrays, which at K = 100 ends at 256 classes."""
+    return bool(nat.lib().ocr_ctc_beam_lm_supported(int(C), int(K), int(H)))
+
+
+def ctc_beam_lm(acts, input_lengths, automaton, top_paths, beam_width=100, blank=0, pad_value=0, workspace=None):
+    """The prefix search of ctc_beam_nbest (merge_repeated=False) fused with an automaton.LabelAutomaton over the caller's class ids: every
+    extension of a prefix also pays the automaton's weight, forbidden transitions are never taken, and the final ranking adds the end weight
+    of the prefix's state.  -> (paths [N, top_paths, T] int32, lengths [N, top_paths] int32, neg_log_prob [N, top_paths] f32 = minus the fused
+    score, lm_score [N, top_paths] f32 = the automaton's share of it (automaton.score(labels)), count [N] int32); slots at and beyond
+    count[n] hold pad_value / -1 / +inf / -inf.  -neg_log_prob - lm_score is the beam's acoustic log-probability of the string."""
+    T, N, C = acts.shape
+    _dev(acts)
+    if automaton.num_classes != C:
+        raise ValueError('logits of %d classes, a LabelAutomaton built for %d' % (C, automaton.num_classes))
+    top_paths, blank = int(top_paths), int(blank)
+    if 0 <= blank < C and automaton.blank != blank:              # (a blank outside the alphabet is the entry's to refuse)
+        raise ValueError('blank %d, but the LabelAutomaton was built with blank %d' % (blank, automaton.blank))
+    nxt, weight, final = automaton.device_arrays(acts.device)
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_beam_lm_workspace_size", C, N, T, beam_width, ctypes.byref(sz))
+    if workspace is None or workspace.numel() < sz.value:
+        workspace = torch.empty(sz.value, dtype=torch.uint8, device=acts.device)
+    shape = (N, max(top_paths, 0))                 # (a top_paths outside the limits is the entry's to refuse)
+    paths = torch.empty(shape + (T,), dtype=torch.int32, device=acts.device)
+    lens = torch.empty(shape, dtype=torch.int32, device=acts.device)
+    nlp = torch.empty(shape, dtype=F32, device=acts.device)
+    lm_score = torch.empty(shape, dtype=F32, device=acts.device)
+    count = torch.empty(N, dtype=torch.int32, device=acts.device)
+    call("ocr_ctc_beam_decode_lm", ptr(acts), ptr(input_lengths), C, N, T, beam_width, top_paths, blank, pad_value, ptr(nxt), ptr(weight),
+         ptr(final), automaton.num_states, ptr(paths), ptr(lens), ptr(nlp), ptr(lm_score), ptr(count), ptr(workspace), workspace.numel(), _st())
+    return paths, lens, nlp, lm_score, count
 
 
 BEAM_KERNEL_NAMES = (None, "table", "wide")
