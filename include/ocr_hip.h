@@ -273,6 +273,35 @@ int ocr_ctc_beam_decode_lm(const float* activations, const int* input_lengths, i
                            const int* lm_next, const float* lm_weight, const float* lm_final, int num_states,
                            int* decoded, int* decoded_lengths, float* neg_log_prob, float* lm_score, int* count,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* The fused search for wide alphabets: ocr_ctc_beam_decode_lm with the automaton in a sparse form with failure (back-off) transitions, whose
+ * size follows the arcs that exist (automaton.SparseLabelAutomaton).  num_states = H states, start state 0, num_arcs = A arcs:
+ *   arc_begin: int32 [H + 1], the arcs of state s are arc_begin[s] .. arc_begin[s + 1] - 1;  arc_label: int32 [A], the caller's class ids,
+ *   ascending within a state;  arc_next: int32 [A];  arc_weight: f32 [A];  backoff: int32 [H] (-1 = none);  backoff_weight: f32 [H];
+ *   lm_final: f32 [H].
+ * Reading class c in state s: the arcs of s are searched for c by bisection.  A hit pays the accumulated back-off weights plus arc_weight
+ * (summed in float32 in hop order, the arc weight last) and moves to arc_next; it is forbidden when arc_weight or the sum is not finite or
+ * arc_next lies outside [0, H).  A miss pays backoff_weight[s] and retries in backoff[s] when that lies in [0, H) and the weight is finite,
+ * at most 8 times; otherwise the transition is forbidden.  Every arc range is clamped to [0, A] (an inverted one is empty) and every
+ * arc_next and backoff is bounds-checked: no array content makes the kernel read outside the arrays or loop; labels that are not
+ * ascending only make lookups miss.
+ * New children of a frame are restricted to its min(cutoff, alphabet_size - 1) likeliest non-blank classes (ties at the boundary to the
+ * lowest class), 1 <= cutoff <= beam_width + 1: with weights in the search this acoustic pruning is part of the result, not an exact
+ * shortcut.  A child that is already in the beam receives its parent's mass whatever its class.  Everything else - total, ranking,
+ * outputs, the slots beyond count[n], the workspace layout and size - is ocr_ctc_beam_decode_lm's.
+ * Supported (ocr_ctc_beam_lm_sparse_supported, host-only, 1 / 0): 2 <= alphabet_size <= 16384, 1 <= beam_width <= 128, the cutoff range
+ * above, 1 <= num_states <= 1 << 24, 0 <= num_arcs <= 1 << 28, and the wide kernel's LDS at min(cutoff, alphabet_size - 1) candidate classes
+ * plus 2048 bytes <= 160 KB (which holds for every such shape).  It always runs the wide kernel, whatever ocr_set_beam_engine says.
+ * 1 <= top_paths <= beam_width, 0 <= blank < alphabet_size, none of the operands may be NULL; anything else is OCR_STATUS_INVALID,
+ * nothing is launched and no output is written.  With one state, an arc of weight 0 to itself for every class, final 0 and
+ * cutoff = beam_width + 1 the outputs are the wide kernel's ocr_ctc_beam_decode_nbest (merge_repeated = 0) bit for bit, lm_score 0. */
+int ocr_ctc_beam_lm_sparse_supported(int alphabet_size, int beam_width, int cutoff, int num_states, int num_arcs);
+int ocr_ctc_beam_lm_sparse_workspace_size(int alphabet_size, int minibatch, int max_time, int beam_width, size_t* bytes);
+int ocr_ctc_beam_decode_lm_sparse(const float* activations, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
+                                  int beam_width, int cutoff, int top_paths, int blank, int pad_value,
+                                  const int* arc_begin, const int* arc_label, const int* arc_next, const float* arc_weight,
+                                  const int* backoff, const float* backoff_weight, const float* lm_final, int num_states, int num_arcs,
+                                  int* decoded, int* decoded_lengths, float* neg_log_prob, float* lm_score, int* count,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 /* Which kernel ocr_ctc_beam_decode runs for a shape - a host-only query like ocr_conv3x3_kernel_choice (nothing is launched, works
  * without a GPU): 0 refused, 1 table kernel, 2 wide kernel.  It honours ocr_set_beam_engine. */
 int ocr_ctc_beam_kernel_choice(int alphabet_size, int beam_width);

@@ -61,6 +61,10 @@ _SIGS = {
     "ocr_ctc_beam_lm_supported": ([_I, _I, _I], _I),
     "ocr_ctc_beam_lm_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
     "ocr_ctc_beam_decode_lm": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P], _I),
+    "ocr_ctc_beam_lm_sparse_supported": ([_I, _I, _I, _I, _I], _I),
+    "ocr_ctc_beam_lm_sparse_workspace_size": ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)], _I),
+    "ocr_ctc_beam_decode_lm_sparse": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P,
+                                       ctypes.c_size_t, _P], _I),
     "ocr_ctc_beam_kernel_choice": ([_I, _I], _I),
     "ocr_set_beam_engine": ([_I], _I),
     "ocr_gemm_nt_bf16": ([_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P], _I),

@@ -41,6 +41,15 @@
 // pnb[s] and the blank term pay nothing.  Pruning ranks by total; the final ranking adds final[state].  A transition is forbidden when its
 // weight is not finite or its next state lies outside [0, num_states): every state the kernel holds is in range, so no table content
 // makes it read outside the tables.
+//
+// LM = true with WIDE = true is ocr_ctc_beam_decode_lm_sparse: the same terms on the wide kernel, the automaton in the sparse form with failure
+// (back-off) arcs of automaton.SparseLabelAutomaton.  Its size follows the arcs that exist, so a bigram or a lexicon trie over thousands of
+// classes fits.  sparse_step walks at most SPARSE_MAX_HOPS back-off hops, each a binary search among the state's arcs; every arc range is
+// clamped to [0, num_arcs], every arc_next and backoff is bounds-checked and the hop count is capped, so no array content makes the kernel
+// read outside the arrays or loop.  With weights in the search the wide kernel's "the K + 1 likeliest classes lose nothing" no longer
+// holds (a class outside S may carry a large weight), so here the selection is part of the specification: new children are restricted to
+// the M = min(cutoff, C - 1) likeliest non-blank classes of the frame, the acoustic pruning of every practical decoder.  A child that is
+// in the beam still takes its parent's mass in step (b) whatever its class.
 #include "common.h"
 #include <float.h>
 #include <math.h>
@@ -75,6 +84,37 @@ struct BeamLmArgs : BeamArgs {
     float* lm_score;
 };
 __device__ __forceinline__ bool lm_finite(float w) { return fabsf(w) <= FLT_MAX; }       // false for -inf, +inf and NaN
+// the sparse fused entry's operands: an argument struct of its own, so every other instance keeps its kernel arguments
+struct BeamSparseArgs : BeamArgs {
+    const int* arc_begin; const int* arc_label; const int* arc_next; const float* arc_weight;      // [H + 1], [A], [A], [A]: the caller's class ids
+    const int* backoff; const float* backoff_weight; const float* lm_final;                        // [H], [H], [H]
+    int num_states, num_arcs, cutoff;
+    int* node_state; float* node_w;
+    float* lm_score;
+};
+#define SPARSE_MAX_HOPS 8
+// Reading the caller's class c in state s (0 <= s < num_states): true and (w, next) when the transition exists.  The arcs of s are searched
+// for c (lower bound by bisection; labels that are not ascending only make the search miss); a miss retries in backoff[s] after paying
+// backoff_weight[s], at most SPARSE_MAX_HOPS times.  w = ((bw_1 + bw_2) + ..) + arc_weight in float32, which the host reproduces to the bit.
+__device__ __forceinline__ bool sparse_step(const BeamSparseArgs& a, int s, int c, float& w, int& next) {
+    float acc = 0.f;
+    for (int hops = 0;; ++hops) {
+        int lo = min(max(a.arc_begin[s], 0), a.num_arcs);
+        const int end = min(max(a.arc_begin[s + 1], 0), a.num_arcs);
+        int hi = max(end, lo);                               // an inverted range is empty
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.arc_label[mid] < c) lo = mid + 1; else hi = mid; }
+        if (lo < end && a.arc_label[lo] == c) {
+            const float aw = a.arc_weight[lo];
+            const unsigned nx = (unsigned)a.arc_next[lo];
+            w = acc + aw; next = (int)nx;
+            return lm_finite(aw) && lm_finite(w) && nx < (unsigned)a.num_states;
+        }
+        const unsigned bo = (unsigned)a.backoff[s];
+        const float bw = a.backoff_weight[s];
+        if (hops == SPARSE_MAX_HOPS || bo >= (unsigned)a.num_states || !lm_finite(bw)) return false;
+        acc += bw; s = (int)bo;
+    }
+}
 
 // NBEST = true is ocr_ctc_beam_decode_nbest: the caller's blank is any class and the `top_paths` best leaves are emitted.  Inside the
 // kernel the blank stays the LAST class: the log-softmax row is stored through the monotone re-indexing  k -> k (k < blank),
@@ -85,14 +125,16 @@ __device__ __forceinline__ bool lm_finite(float w) { return fabsf(w) <= FLT_MAX;
 // LM = true is ocr_ctc_beam_decode_lm (see the header): NBEST's re-indexing and emission, the automaton's terms in steps (b), (c), (f) and in
 // the final ranking.  Its tables are indexed by the caller's class ids: internal class c is the caller's  c < blank ? c : c + 1.
 template <bool WIDE, bool NBEST, bool LM = false>
-__global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<LM, BeamLmArgs, BeamArgs> a) {
-    static_assert(!LM || (NBEST && !WIDE), "the fused search runs on the table kernel with the n-best emission");
+__global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<LM, std::conditional_t<WIDE, BeamSparseArgs, BeamLmArgs>, BeamArgs> a) {
+    static_assert(!LM || NBEST, "the fused search emits through the n-best path");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = a.C, K = a.K, blank = C - 1;
     const int Tn = min(a.input_len[n], a.T);
     const int pool = a.T * K + 2;
-    const int M = WIDE ? min(K + 1, C - 1) : C;           // candidate classes per beam entry (the table kernel scores all C)
+    int Msel = WIDE ? min(K + 1, C - 1) : C;              // candidate classes per beam entry (the table kernel scores all C)
+    if constexpr (WIDE && LM) Msel = min(a.cutoff, C - 1);   // the sparse fused entry: the caller's acoustic cutoff, 1 <= cutoff <= K + 1
+    const int M = Msel;
     int* npar = a.node_parent + (size_t)n * pool;
     short* nlab = a.node_label + (size_t)n * pool;
     int* nslot = a.node_slot + (size_t)n * pool;
@@ -246,7 +288,13 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<LM, Be
             for (int i = tid; i < nb * M; i += 256) {
                 const int b = i / M, c = sel_cls[i - b * M];
                 const float prev = (c == last[b]) ? pb[b] : tot[b];
-                cand[nb + i] = (prev != NEGINF) ? prev + lp[c] : NEGINF;
+                if constexpr (LM) {
+                    float v = NEGINF, w; int nx;
+                    if (prev != NEGINF && sparse_step(a, state[b], c < a.blank ? c : c + 1, w, nx)) v = prev + lp[c] + w;
+                    cand[nb + i] = v;
+                } else {
+                    cand[nb + i] = (prev != NEGINF) ? prev + lp[c] : NEGINF;
+                }
             }
             __syncthreads();
             // a beam entry whose parent is in the beam cancels the candidate (parent, own label), if its label is in S
@@ -356,7 +404,10 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(std::conditional_t<LM, Be
                 if (id < 0) {
                     id = atomicAdd(&s_misc[1], 1);
                     npar[id] = node[b]; nlab[id] = (short)c;
-                    if constexpr (LM) {                     // admitted, so step (c) found the weight finite and the next state in range
+                    if constexpr (LM && WIDE) {             // admitted, so step (c) found this transition: the same walk, the same (w, next)
+                        if (!sparse_step(a, state[b], c < a.blank ? c : c + 1, r_w, r_state)) { r_state = 0; r_w = NEGINF; }      // (never taken)
+                        nstate[id] = r_state; nw[id] = r_w;
+                    } else if constexpr (LM) {              // admitted, so step (c) found the weight finite and the next state in range
                         const size_t e = (size_t)state[b] * C + (c < a.blank ? c : c + 1);
                         r_state = a.lm_next[e]; r_w = a.lm_weight[e];
                         nstate[id] = r_state; nw[id] = r_w;
@@ -595,6 +646,63 @@ extern "C" int ocr_ctc_beam_decode_lm(const float* activations, const int* input
     const size_t lds = beam_lm_lds_bytes(alphabet_size, beam_width);
     if (ocr_allow_lds<ctc_beam_kernel<false, true, true>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
     ctc_beam_kernel<false, true, true><<<minibatch, 256, lds, stream>>>(a);
+    OCR_CHECK_LAUNCH();
+    return OCR_OK;
+}
+
+// ---- the search fused with a sparse back-off automaton (LM = true on the wide kernel, whatever ocr_set_beam_engine says)
+#define BEAM_SPARSE_MAX_STATES (1 << 24)
+#define BEAM_SPARSE_MAX_ARCS (1 << 28)
+static size_t beam_sparse_lds_bytes(int C, int K, int cutoff) {      // the wide kernel's with M = min(cutoff, C - 1), and b_state / b_w
+    const size_t M = (size_t)((cutoff < C - 1) ? cutoff : C - 1);
+    size_t b = (size_t)((C + 3) & ~3) * 4 + ((size_t)K + (size_t)K * M) * 4 + M * 4 + (size_t)BEAM_MAX * 2 * 6 * 4 + (size_t)BEAM_MAX * 4;
+    return ((b + 15) & ~(size_t)15) + (size_t)BEAM_MAX * 2 * 2 * 4;
+}
+extern "C" int ocr_ctc_beam_lm_sparse_supported(int alphabet_size, int beam_width, int cutoff, int num_states, int num_arcs) {
+    if (alphabet_size < 2 || alphabet_size > BEAM_WIDE_MAX_C || beam_width < 1 || beam_width > BEAM_MAX) return 0;
+    if (cutoff < 1 || cutoff > beam_width + 1) return 0;
+    if (num_states < 1 || num_states > BEAM_SPARSE_MAX_STATES || num_arcs < 0 || num_arcs > BEAM_SPARSE_MAX_ARCS) return 0;
+    return beam_sparse_lds_bytes(alphabet_size, beam_width, cutoff) <= BEAM_LDS_LIMIT ? 1 : 0;
+}
+// per pool entry what ocr_ctc_beam_lm_workspace_size counts: node_parent, node_slot, node_state (int), node_w (float), node_label (short)
+extern "C" int ocr_ctc_beam_lm_sparse_workspace_size(int alphabet_size, int minibatch, int max_time, int beam_width, size_t* bytes) {
+    if (!bytes || minibatch <= 0 || max_time <= 0 || !ocr_ctc_beam_lm_sparse_supported(alphabet_size, beam_width, 1, 1, 0)) return OCR_ERR_INVALID;
+    const size_t pool = (size_t)max_time * beam_width + 2;
+    *bytes = (size_t)minibatch * pool * (sizeof(int) * 3 + sizeof(float) + sizeof(short));
+    *bytes = (*bytes + 255) & ~(size_t)255;
+    return OCR_OK;
+}
+// Outputs and refusals as ocr_ctc_beam_decode_lm's; new children of a frame come from its min(cutoff, C - 1) likeliest non-blank classes.
+extern "C" int ocr_ctc_beam_decode_lm_sparse(const float* activations, const int* input_lengths, int alphabet_size, int minibatch, int max_time,
+                                             int beam_width, int cutoff, int top_paths, int blank, int pad_value, const int* arc_begin,
+                                             const int* arc_label, const int* arc_next, const float* arc_weight, const int* backoff,
+                                             const float* backoff_weight, const float* lm_final, int num_states, int num_arcs, int* decoded,
+                                             int* decoded_lengths, float* neg_log_prob, float* lm_score, int* count, void* workspace,
+                                             size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    size_t need = 0;
+    if (!activations || !input_lengths || !arc_begin || !arc_label || !arc_next || !arc_weight || !backoff || !backoff_weight || !lm_final ||
+        !decoded || !decoded_lengths || !neg_log_prob || !lm_score || !count || !workspace)
+        return OCR_ERR_INVALID;
+    if (!ocr_ctc_beam_lm_sparse_supported(alphabet_size, beam_width, cutoff, num_states, num_arcs)) return OCR_ERR_INVALID;
+    if (ocr_ctc_beam_lm_sparse_workspace_size(alphabet_size, minibatch, max_time, beam_width, &need) != OCR_OK || workspace_bytes < need)
+        return OCR_ERR_INVALID;
+    if (top_paths < 1 || top_paths > beam_width || blank < 0 || blank >= alphabet_size) return OCR_ERR_INVALID;
+    BeamSparseArgs a;
+    (BeamArgs&)a = {activations, input_lengths, max_time, minibatch, alphabet_size, beam_width, 0, pad_value,
+                    decoded, decoded_lengths, neg_log_prob, nullptr, nullptr, nullptr, blank, top_paths, count};
+    const size_t pool = (size_t)max_time * beam_width + 2, all = (size_t)minibatch * pool;
+    a.node_parent = (int*)workspace;
+    a.node_slot = a.node_parent + all;
+    a.node_state = a.node_slot + all;
+    a.node_w = (float*)(a.node_state + all);
+    a.node_label = (short*)(a.node_w + all);
+    a.arc_begin = arc_begin; a.arc_label = arc_label; a.arc_next = arc_next; a.arc_weight = arc_weight;
+    a.backoff = backoff; a.backoff_weight = backoff_weight; a.lm_final = lm_final;
+    a.num_states = num_states; a.num_arcs = num_arcs; a.cutoff = cutoff; a.lm_score = lm_score;
+    const size_t lds = beam_sparse_lds_bytes(alphabet_size, beam_width, cutoff);
+    if (ocr_allow_lds<ctc_beam_kernel<true, true, true>>((int)lds) != hipSuccess) return OCR_ERR_EXEC;
+    ctc_beam_kernel<true, true, true><<<minibatch, 256, lds, stream>>>(a);
     OCR_CHECK_LAUNCH();
     return OCR_OK;
 }

@@ -25,7 +25,7 @@ from . import ops
 from ._native import NativeError, call as nat_call
 from .engine_ops import (BF16, F32, I32, _env, _number, _switch, _AddOp, _AvgPoolOp, _BatchNormOp, _BiLstmOp, _ConcatOp, _ConvOp,
                          _Conv3x3Op, _DropoutOp, _FcOp, _InputOp, _PoolOp, _ReluOp, _SoftmaxOp, _SubsampleOp, _ViewOp, _conv_op)
-from .automaton import LabelAutomaton
+from .automaton import LabelAutomaton, SparseLabelAutomaton
 from .lexicon import LexiconTrie
 from .layout import FlatLayout, execution_order, init_host_parameters
 
@@ -942,16 +942,17 @@ class Engine(object):
     def decode_lm(self, data, seq_len, lm, beam_width=100):
         """decode(method='prefix') with the search fused with `lm`, an automaton.LabelAutomaton over the classes (blank 0): a language model
         (LabelAutomaton.from_ngram) or a constraint (from_lexicon, from_pattern) steers the beam itself (ops.ctc_beam_lm) where
-        rescoring.rerank only re-orders what the acoustic beam kept.  -> the best string per sample under log p_beam + automaton.score; [] for
+        rescoring.rerank only re-orders what the acoustic beam kept.  An automaton.SparseLabelAutomaton (from_backoff_ngram, from_lexicon: any
+        alphabet up to 16384 classes) runs the wide kernel's fused search (ops.ctc_beam_lm_sparse) instead.  -> the best string per sample under log p_beam + automaton.score; [] for
         a sample for which the automaton accepts nothing in the beam.  (A method of its own: decode's signature is pinned.)"""
         return self._decode(data, seq_len, 'prefix', beam_width, None, self._check_lm(lm))
 
     @staticmethod
     def _check_lm(lm):
-        if not isinstance(lm, LabelAutomaton):
+        if not isinstance(lm, (LabelAutomaton, SparseLabelAutomaton)):
             raise ValueError('lm must be an automaton.LabelAutomaton (got %s)' % type(lm).__name__)
         if lm.blank != 0:
-            raise ValueError('blank 0, but the LabelAutomaton was built with blank %d' % lm.blank)
+            raise ValueError('blank 0, but the %s was built with blank %d' % (type(lm).__name__, lm.blank))
         return lm
 
     def _decode(self, data, seq_len, method, beam_width, lexicon, lm):
@@ -986,7 +987,8 @@ class Engine(object):
         -> (paths, lengths, neg_log_prob, count, lm_score or None)."""
         if lm is None:
             return ops.ctc_beam_nbest(logits, seq_len, top_paths, beam_width=beam_width, blank=0, merge_repeated=False, pad_value=0) + (None,)
-        paths, lens, nlp, lm_score, count = ops.ctc_beam_lm(logits, seq_len, lm, top_paths, beam_width=beam_width, blank=0, pad_value=0)
+        search = ops.ctc_beam_lm_sparse if isinstance(lm, SparseLabelAutomaton) else ops.ctc_beam_lm      # (the sparse entry at its default cutoff)
+        paths, lens, nlp, lm_score, count = search(logits, seq_len, lm, top_paths, beam_width=beam_width, blank=0, pad_value=0)
         return paths, lens, nlp, count, lm_score
 
     SCORE_MAX_LABEL_LEN = 255

@@ -472,6 +472,41 @@ def ctc_beam_lm(acts, input_lengths, automaton, top_paths, beam_width=100, blank
     return paths, lens, nlp, lm_score, count
 
 
+def ctc_beam_lm_sparse_supported(C, K, cutoff, H, A):
+    """Whether ctc_beam_lm_sparse covers C classes at beam width K and class cutoff `cutoff` with an automaton of H states and A arcs (host
+    arithmetic only): 2 <= C <= 16384, K <= 128, 1 <= cutoff <= K + 1, H <= 1 << 24, A <= 1 << 28."""
+    return bool(nat.lib().ocr_ctc_beam_lm_sparse_supported(int(C), int(K), int(cutoff), int(H), int(A)))
+
+
+def ctc_beam_lm_sparse(acts, input_lengths, automaton, top_paths, beam_width=100, cutoff=None, blank=0, pad_value=0, workspace=None):
+    """ctc_beam_lm for wide alphabets (up to 16384 classes): the search runs on the wide kernel and reads an automaton.SparseLabelAutomaton,
+    whose failure arcs are followed on the device.  New children of a frame come from its min(cutoff, C - 1) likeliest non-blank classes
+    (None: beam_width + 1); with weights in the search that acoustic pruning is part of the result.  Outputs as ctc_beam_lm's."""
+    T, N, C = acts.shape
+    _dev(acts)
+    if automaton.num_classes != C:
+        raise ValueError('logits of %d classes, a SparseLabelAutomaton built for %d' % (C, automaton.num_classes))
+    top_paths, blank = int(top_paths), int(blank)
+    cutoff = int(beam_width) + 1 if cutoff is None else int(cutoff)
+    if 0 <= blank < C and automaton.blank != blank:              # (a blank outside the alphabet is the entry's to refuse)
+        raise ValueError('blank %d, but the SparseLabelAutomaton was built with blank %d' % (blank, automaton.blank))
+    arrays = automaton.device_arrays(acts.device)
+    sz = ctypes.c_size_t(0)
+    call("ocr_ctc_beam_lm_sparse_workspace_size", C, N, T, beam_width, ctypes.byref(sz))
+    if workspace is None or workspace.numel() < sz.value:
+        workspace = torch.empty(sz.value, dtype=torch.uint8, device=acts.device)
+    shape = (N, max(top_paths, 0))                 # (a top_paths outside the limits is the entry's to refuse)
+    paths = torch.empty(shape + (T,), dtype=torch.int32, device=acts.device)
+    lens = torch.empty(shape, dtype=torch.int32, device=acts.device)
+    nlp = torch.empty(shape, dtype=F32, device=acts.device)
+    lm_score = torch.empty(shape, dtype=F32, device=acts.device)
+    count = torch.empty(N, dtype=torch.int32, device=acts.device)
+    call("ocr_ctc_beam_decode_lm_sparse", ptr(acts), ptr(input_lengths), C, N, T, beam_width, cutoff, top_paths, blank, pad_value,
+         *[ptr(v) for v in arrays], automaton.num_states, automaton.num_arcs, ptr(paths), ptr(lens), ptr(nlp), ptr(lm_score), ptr(count),
+         ptr(workspace), workspace.numel(), _st())
+    return paths, lens, nlp, lm_score, count
+
+
 BEAM_KERNEL_NAMES = (None, "table", "wide")
 
 
